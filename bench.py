@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: batched CRC32C over device-resident 4 KiB SST blocks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--nblocks B] [--strong] [--no-gather] [--e2e]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--nblocks B] [--strong] [--no-gather]
+                    [--dump-outputs DIR] [--full [--e2e]]
+
+A plain run does what the headline needs and no more: it sets up, warms up,
+times the K steps, writes the last step's results if --dump-outputs is given
+and prints the line.  --full adds every other leg listed below.
 
 Workload (BASELINE.json configs[1], "config 2"): per GPU, 16 Mi blocks x 4096 B
 (64 GiB) generated on the device from the splitmix64 stream, stride 4096,
@@ -18,12 +23,24 @@ exits with its status; a WORLD_SIZE that disagrees with --gpus is an error.
 per rank), and --no-gather drops the RCCL gather
 (config 5 asks for both).
 
+--dump-outputs DIR writes what the last timed step returned to its caller:
+DIR/crc32c.npy (N > 1: DIR/crc32c_rank<r>.npy, each rank its own shard), the
+step's u32 results as float64 (exact).  At most 4 Mi entries (32 MiB) over all
+ranks: of a larger result a fixed sample, drawn in ascending block order by a
+generator seeded with the bench's seed.  The blocks are the same splitmix64
+stream in every run, so two builds can be compared entry for entry.
+
 Printed (rank 0): ONE JSON line with the driver's contract fields plus
-  roofline      dominant kernel vs the HBM roofline (HIP events on the launch stream)
+  roofline      dominant kernel vs the HBM roofline (HIP events on the launch
+                stream of the timed steps); its `traffic` from the committed
+                PMC summary with --full only
+and, with --full:
+  gather_check  (N > 1) digests of every rank's last results against what
+                rank 0 received
   cpu_baseline  the reference crc32c::Value (util/crc32c.cc compiled to
                 oracle/_ref/) on this host's cores over a bounded sample of the
                 same blocks, also cross-checked bit for bit against the GPU results
-  e2e           (with --e2e) host-resident rate incl. pinned H2D/D2H copies
+  e2e           (with --full --e2e) host-resident rate incl. pinned H2D/D2H copies
   config5_partitions
                 BASELINE configs[4]: each rank one PrismDB partition of ~2.4 M
                 SST block spans (143 files), sealed and verified file by file
@@ -76,10 +93,16 @@ def parse():
     ap.add_argument("--nblocks", type=int, default=1 << 24, help="4 KiB blocks per GPU (--strong: in total)")
     ap.add_argument("--strong", action="store_true", help="strong scaling: --nblocks is the total over all ranks")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: no RCCL gather of the results")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/<name>.npy (float64; at most 4 Mi entries)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: cpu_baseline, the config-5 legs, the gather check, "
+                         "the committed PMC traffic, and --e2e's legs")
     ap.add_argument("--cpu-sample-blocks", type=int, default=1 << 18)
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-seconds of reference work")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--e2e", action="store_true", help="also measure the host-resident (pinned copy) rate")
+    ap.add_argument("--e2e", action="store_true",
+                    help="with --full: also measure the host-resident (pinned copy) rate")
     ap.add_argument("--no-config5", action="store_true", help="skip the config-5 partition leg")
     ap.add_argument("--c5-spans", type=int, default=2_400_000, help="config-5 spans per partition (GPU)")
     # (20, as the headline's steps: at 5 the first call's launch latency and
@@ -97,7 +120,10 @@ def parse():
                     help="at --gpus 1: devices of the one-process batch_multi leg (default 1)")
     ap.add_argument("--cpu-all-blocks", type=int, default=1 << 20,
                     help="cpu_baseline all-cores figure: blocks (config 1: 1 Mi x 4 KiB)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.e2e and not args.full:
+        ap.error("--e2e is one of the --full legs: pass --full --e2e")
+    return args
 
 
 def affinity() -> list:
@@ -657,6 +683,28 @@ def multi_leg(args, torch, crc32c, ndev: int) -> dict:
     return res
 
 
+DUMP_MAX_ENTRIES = 1 << 22  # float64: 32 MiB over all ranks
+
+
+def dump_outputs(path: str, out, rank: int, world: int) -> None:
+    """--dump-outputs: the last timed step's results (int32 bits of the u32
+    CRCs, on the device) as float64 in DIR/crc32c.npy (world > 1: this rank's
+    shard in DIR/crc32c_rank<r>.npy).  A result longer than this rank's share
+    of DUMP_MAX_ENTRIES is sampled: entries drawn without replacement by a
+    generator seeded with SEED (and the rank), in ascending order -- the same
+    entries in every run with the same arguments."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    got = out.cpu().numpy().view(np.uint32)
+    cap = max(1, DUMP_MAX_ENTRIES // world)
+    if got.size > cap:
+        pick = np.sort(np.random.default_rng([SEED, rank]).choice(got.size, size=cap, replace=False))
+        got = got[pick]
+    name = "crc32c.npy" if world == 1 else f"crc32c_rank{rank}.npy"
+    np.save(os.path.join(path, name), got.astype(np.float64))
+
+
 def free_port() -> int:
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
         so.bind(("127.0.0.1", 0))
@@ -808,19 +856,23 @@ def main() -> int:
     value = total_bytes / elapsed / GIB
     algo_bytes = nblk * (BLOCK + 4)  # L read + 4 B result written per block
     achieved = algo_bytes / (kern_ms / 1e3) / 1e9
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, outs[(args.steps - 1) % 2], rank, world)
+    # Everything from here to the line is --full's: a plain run has measured
+    # all its line holds.
     # rank-0 results check: gathered results of the last step hold every rank's shard
     gathered_ok = None
-    if gather:
+    if gather and args.full:
         gathered_ok = shard.check_gathered(outs[(args.steps - 1) % 2])
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_leg(args, outs[(args.steps - 1) % 2], buf)
-    e2e = e2e_leg(args, torch, crc32c, dev) if (args.e2e and rank == 0 and world == 1) else None
+    e2e = e2e_leg(args, torch, crc32c, dev) if (args.full and args.e2e and rank == 0 and world == 1) else None
     del buf  # the config-2 blocks; the results stay for the checks above
     torch.cuda.empty_cache()
     c5 = None
-    if not args.no_config5:
+    if args.full and not args.no_config5:
         if world == 1:
             try:  # one rank: a failure here is reported in the line, the headline stands
                 c5 = config5_leg(args, torch, dist, crc32c, dev, rank, world)
@@ -829,7 +881,7 @@ def main() -> int:
         else:  # (ranks meet in collectives inside: one rank's exception must end them all)
             c5 = config5_leg(args, torch, dist, crc32c, dev, rank, world)
     multi = None
-    if not args.no_multi:
+    if args.full and not args.no_multi:
         # one child process of rank 0 drives the devices (all `world` ranks'
         # devices: PrismDB's one-process shape); the ranks free their memory
         # and wait on the host
@@ -846,7 +898,7 @@ def main() -> int:
             dist.barrier(group=cpu_group)
 
     if rank == 0:
-        pmc = load_pmc_traffic(nblk)
+        pmc = load_pmc_traffic(nblk) if args.full else None
         line = {
             "metric": METRIC,
             "value": round(value, 2),

@@ -96,6 +96,49 @@ def test_multi_leg_child_reports_instead_of_raising(monkeypatch):
     assert res == {"devices": 2, "error": "batch_multi leg stopped after 0 s"}
 
 
+def test_full_is_off_by_default_and_e2e_needs_it(monkeypatch, capsys):
+    """A plain run asks for none of the legs beyond the headline; --e2e is
+    one of --full's legs and is refused without it."""
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", [BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 3
+    monkeypatch.setattr(sys, "argv", [BENCH, "--full", "--e2e", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full and args.e2e and args.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", [BENCH, "--e2e"])
+    with pytest.raises(SystemExit) as e:
+        bench.parse()
+    assert e.value.code == 2
+    assert "--full" in capsys.readouterr().err
+
+
+def test_dump_outputs_exact_and_sample_fixed(tmp_path, monkeypatch):
+    """--dump-outputs: u32 results exact in float64 (the sign bit included);
+    a result longer than the cap is the same ascending sample in every run,
+    another one per rank."""
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    u = np.random.default_rng(7).integers(0, 1 << 32, size=1000, dtype=np.uint64).astype(np.uint32)
+    u[:2] = (0xFFFFFFFF, 0x80000000)
+    out = torch.from_numpy(u.view(np.int32).copy())
+    bench.dump_outputs(str(tmp_path / "a"), out, 0, 1)
+    got = np.load(tmp_path / "a" / "crc32c.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, u.astype(np.float64))
+    monkeypatch.setattr(bench, "DUMP_MAX_ENTRIES", 128)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), out, 0, 1)
+        bench.dump_outputs(str(tmp_path / d), out, 1, 2)
+    b, c = np.load(tmp_path / "b" / "crc32c.npy"), np.load(tmp_path / "c" / "crc32c.npy")
+    assert b.shape == (128,) and np.array_equal(b, c)
+    assert np.isin(b, u.astype(np.float64)).all()
+    r1 = np.load(tmp_path / "b" / "crc32c_rank1.npy")
+    assert r1.shape == (64,) and np.array_equal(r1, np.load(tmp_path / "c" / "crc32c_rank1.npy"))
+    assert not np.array_equal(r1, b[:64])
+
+
 def test_pmc_summary_picked_is_the_newest():
     """The line's `traffic` comes from the newest committed PMC summary of
     the headline workload: by round, then run tag (r05ab after r05g after

@@ -109,6 +109,19 @@ std::atomic<uint32_t> g_direct_dbg{0};
 // random spans 70.3 against 77.1 %), on uniform SST spans they win (72.8
 // against 70.8 %; profiles/r04/r04e_configs.json).
 std::atomic<int> g_windows{2};
+// The grid of the persistent kernels, in workgroups: 0 (the default) = the
+// device's CU count, else min(this, the CU count) -- never more, the kernels'
+// groups are all co-resident.  The tests run every route at reduced grids:
+// each kernel sizes its schedule from the grid it was launched with.
+std::atomic<int> g_grid{0};
+
+// The one value every host use of the CU count goes through: the launched
+// grids and the host's arithmetic on them (the one-launch capacity, the
+// planner's stream count) cannot disagree.
+int Groups(int cus) {
+  const int g = g_grid.load(std::memory_order_relaxed);
+  return g > 0 && g < cus ? g : cus;
+}
 
 void BuildTables(DeviceTables* t) {
   namespace g = prismdb::gf2;
@@ -563,7 +576,7 @@ enum Route { kRouteAuto = 0, kRouteDirect = 1, kRoutePlanner = 2 };
 // the CUs: twelve SST files per call took 18.0 us per file that way against
 // 12.8 us in calls of seven files, profiles/r04/r04g_bench.json.)
 int RunWindows(DeviceCtx& ctx, const SpanBatch& a, bool verify, hipStream_t s, uint64_t wmax) {
-  const uint64_t cap = 64ull * (uint64_t)ctx.cus * (prismdb::dev::kDirectThreads / 64);  // one span run per wave
+  const uint64_t cap = 64ull * (uint64_t)Groups(ctx.cus) * (prismdb::dev::kDirectThreads / 64);  // one span run per wave
   if (wmax > cap) wmax = cap;
   const uint64_t nwin = (a.n + wmax - 1) / wmax;
   uint64_t at = 0;
@@ -598,6 +611,7 @@ int SideStream(Workspace* w) {
 
 int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify, hipStream_t s, int route) {
   SpanBatch a = base_args;
+  const int groups = Groups(ctx.cus);  // read once: this call's grids and its arithmetic on them
   // PRISMDB_CRC32C_UNORDERED is accepted and has no effect: every launch is
   // in stream order (an any-order launch is not supported on gfx9, and it
   // measured slower where it ran: 25.9 against 24.9 us per SST file)
@@ -613,7 +627,7 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
       a.len_c >= 4 && a.len_c <= max_len && (a.len_c & 3u) == 0 &&
       (a.stride & 3u) == 0 && (reinterpret_cast<uintptr_t>(a.base) & 3u) == 0 &&
       !g_force_generic.load(std::memory_order_relaxed)) {
-    hipError_t e = prismdb::dev::launch_fixed(a, verify, ctx.cus, s);
+    hipError_t e = prismdb::dev::launch_fixed(a, verify, groups, s);
     return e == hipSuccess ? 0 : FailHip(e, "fixed kernel launch");
   }
   int rc = 0;
@@ -654,7 +668,7 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
   const bool direct = desc && (route == kRouteDirect ||
                                (route == kRouteAuto && (a.n <= g_direct_max.load(std::memory_order_relaxed) || sst_batch)));
   if (direct && a.n <= prismdb::dev::kDirectMaxSpans &&
-      a.n <= 64ull * (uint64_t)ctx.cus * (prismdb::dev::kDirectThreads / 64)) {
+      a.n <= 64ull * (uint64_t)groups * (prismdb::dev::kDirectThreads / 64)) {
     prismdb::dev::DirectWs d{};
     if ((rc = DirectWorkspace(*w, s, &d)) != 0) return rc;
     t_last_direct = true;
@@ -663,7 +677,7 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
     t_last_owned = w->owned;
     t_last_epoch = g_release_epoch.load(std::memory_order_acquire);
     mark.by_launch = true;
-    hipError_t e = prismdb::dev::launch_direct(a, verify, ctx.cus, d, s, w->done[w->gen & 1u]);
+    hipError_t e = prismdb::dev::launch_direct(a, verify, groups, d, s, w->done[w->gen & 1u]);
     return e == hipSuccess ? 0 : FailHip(e, "direct kernel launch");
   }
   // Bulk descriptor batches: windows of the one-launch kernel.  By default
@@ -705,7 +719,7 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
   // (Round 4 tried one task sequence per wave here, the one-launch kernel's
   // ring: within +-2 % on the bulk rows, profiles/r04/r04i_configs_*.json;
   // its kernels are in git history: crc32c_kernels.hip at 36498f1.)
-  const uint32_t streams = 2u * (uint32_t)ctx.cus * prismdb::dev::kWavesPerGroup;
+  const uint32_t streams = 2u * (uint32_t)groups * prismdb::dev::kWavesPerGroup;
   if ((rc = PlannerWorkspace(*w, s, a.n, streams, lane, &ws)) != 0) return rc;
   // Counters: the block of this call's parity, zeroed by the previous
   // planner call's plan kernel (or at the workspace's creation) -- no fill
@@ -762,7 +776,7 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
     if (e == hipSuccess) e = hipEventRecord(w->join, w->side);
     if (e != hipSuccess) return FailHip(e, "long-span list launch");
     a.claim = &ws.counters->lane_claim;  // (zeroed with the counters above)
-    e = prismdb::dev::launch_lane(a, verify, ctx.cus, s);
+    e = prismdb::dev::launch_lane(a, verify, groups, s);
     if (e == hipSuccess) e = hipStreamWaitEvent(s, w->join, 0);
     if (e != hipSuccess) return FailHip(e, "lane kernel launch");
     side_join.armed = false;
@@ -807,7 +821,7 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
   seg.role = prismdb::dev::kRoleSegments;
   seg.tabs = ctx.tabs;
   seg.rec = ws.seg_rec;
-  e = prismdb::dev::launch_span(seg, false, ctx.cus, w->side, w->join);  // the join: its stop event
+  e = prismdb::dev::launch_span(seg, false, groups, w->side, w->join);  // the join: its stop event
   if (e != hipSuccess) return FailHip(e, "segment kernel launch");
   if (sliced) {
     e = prismdb::dev::launch_slices(a, ws, s);
@@ -826,7 +840,7 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
   t_last_pair = a.pair_kernel != 0u;
   a.claim = &ws.counters->claim;  // (zeroed with the counters above)
   a.claims = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws.counters) + 256);
-  e = prismdb::dev::launch_span(a, verify, ctx.cus, s);
+  e = prismdb::dev::launch_span(a, verify, groups, s);
   if (e != hipSuccess) return FailHip(e, "span kernel launch");
   // The call's last kernel completes the workspace's done event itself (its
   // stop event) instead of a marker after it (MarkDone, on an error return).
@@ -1025,8 +1039,11 @@ void prismdb_crc32c_lane_mode(int mode) {
 }
 
 // descriptor batches of at most this many spans take the one-launch kernel
-// (clamped to kDirectMaxSpans; 0: none do; larger batches: windows of this
-// many spans, see prismdb_crc32c_windows); returns the previous value.
+// (clamped to kDirectMaxSpans; 0: none by size -- with prismdb_crc32c_windows
+// at its default 2 a batch that seals or verifies block trailers still takes
+// it up to its capacity, so a test that pins the planner sets windows 0 too;
+// larger batches: windows of this many spans, see prismdb_crc32c_windows);
+// returns the previous value.
 uint64_t prismdb_crc32c_direct_max(uint64_t n) {
   if (!prismdb::TestHooksEnabled()) return g_direct_max.load(std::memory_order_relaxed);
   if (n > prismdb::dev::kDirectMaxSpans) n = prismdb::dev::kDirectMaxSpans;
@@ -1053,6 +1070,43 @@ uint32_t prismdb_crc32c_direct_debug(uint32_t flags) {
 int prismdb_crc32c_windows(int mode) {
   if (!prismdb::TestHooksEnabled()) return g_windows.load(std::memory_order_relaxed);
   return g_windows.exchange(mode < 0 || mode > 2 ? 2 : mode, std::memory_order_relaxed);
+}
+
+// the persistent kernels' grid in workgroups: 0 = the device's CU count (the
+// default), else min(groups, the CU count); negative values count as 0.
+// Returns the previous value.
+int prismdb_crc32c_grid(int groups) {
+  if (!prismdb::TestHooksEnabled()) return g_grid.load(std::memory_order_relaxed);
+  return g_grid.exchange(groups < 0 ? 0 : groups, std::memory_order_relaxed);
+}
+
+// The pair-run kernel's run deal (prismdb::dev::pair_deal, the function the
+// kernel compiles) for n records on a grid of `groups` workgroups with the
+// claimed tail on: out = {m, K, rq, rr, ptail, Kst, nctr, nwaves}.  Pure host
+// arithmetic: no HIP call, no device, no hook switch.  0, or -1 for an n or a
+// grid no launch has (n = 0 or above the planner's cut, groups = 0 or above
+// 2^16).
+int prismdb_crc32c_pair_deal(uint64_t n, uint32_t groups, uint32_t out[8]) {
+  if (n == 0 || n > prismdb::dev::kMaxGenericSpans || groups == 0 || groups > 65536u || out == nullptr) return -1;
+  const prismdb::dev::PairDeal d = prismdb::dev::pair_deal((uint32_t)n, groups, 0u, true);
+  const uint32_t v[8] = {d.m, d.K, d.rq, d.rr, d.ptail, d.Kst, d.nctr, groups * (uint32_t)prismdb::dev::kWavesPerGroup};
+  std::memcpy(out, v, sizeof(v));
+  return 0;
+}
+// ... every group's claim counter in that deal (out[g], g < groups), and the
+// records [lo[j], hi[j]) of runs k0 + j, j < count (k0 + count <= K).
+int prismdb_crc32c_pair_csets(uint64_t n, uint32_t groups, uint32_t* out) {
+  if (n == 0 || n > prismdb::dev::kMaxGenericSpans || groups == 0 || groups > 65536u || out == nullptr) return -1;
+  for (uint32_t g = 0; g < groups; ++g) out[g] = prismdb::dev::pair_deal((uint32_t)n, groups, g, true).cset;
+  return 0;
+}
+int prismdb_crc32c_pair_runs(uint64_t n, uint32_t groups, uint32_t k0, uint32_t count, uint32_t* lo, uint32_t* hi) {
+  if (n == 0 || n > prismdb::dev::kMaxGenericSpans || groups == 0 || groups > 65536u || lo == nullptr || hi == nullptr)
+    return -1;
+  const prismdb::dev::PairDeal d = prismdb::dev::pair_deal((uint32_t)n, groups, 0u, true);
+  if (k0 > d.K || count > d.K - k0) return -1;
+  for (uint32_t j = 0; j < count; ++j) prismdb::dev::pair_run_bounds(d, (uint32_t)n, k0 + j, lo[j], hi[j]);
+  return 0;
 }
 
 // the call count of the calling thread's workspace for (current device,

@@ -133,6 +133,55 @@ constexpr uint32_t kClaimLines = 8;
 constexpr uint32_t kClaimLineWords = 32;
 constexpr uint32_t kCounterBlock = 256 + kClaimLines * 4 * kClaimLineWords;  // bytes
 
+// The pair-run kernel's run deal (crc32c_pair_kernel; its comment and
+// crc32c_kernels.hip's tuning constants have the measurements), in one place
+// so that the kernel and the host (test hook prismdb_crc32c_pair_deal, the
+// CPU suite's model of the deal) compile the same arithmetic.
+constexpr uint32_t kRunsPerStream = 64;   // one-task runs shrink until every stream (wave) gets this many
+constexpr uint32_t kPairTailRounds = 16;  // the pair-run kernel's last rounds of runs, claimed on demand
+// n records in np = ceil(n / 2) pairs, nwaves = groups * kWavesPerGroup
+// waves: K = min(m * nwaves, np) runs of rq or rq + 1 pairs (runs 0..rr-1 the
+// longer; <= 32 pairs), run k records [lo, hi) (run_bounds).  Runs k < Kst are
+// dealt statically (wave w: w, w + nwaves, ...); the last ptail rounds, Kst..K-1,
+// are claimed on demand (with_claims, and runs of >= 3 pairs) from nctr claim
+// counters: counter c, shared by the groups b with (b / 8) % nctr == c, deals
+// Kst + c + nctr * j for its j-th claim.  nctr is sized from the grid --
+// kClaimLines from 64 groups on, fewer below, where (b / 8) % kClaimLines
+// left counters without a group and their runs unfolded -- so every counter
+// has a group.
+struct PairDeal {
+  uint32_t m, K, rq, rr, ptail, Kst;
+  uint32_t nctr;  // claim counters in use (1..kClaimLines)
+  uint32_t cset;  // the group's counter (< nctr)
+};
+__host__ __device__ inline PairDeal pair_deal(uint32_t n, uint32_t groups, uint32_t group, bool with_claims) {
+  PairDeal d;
+  const uint32_t nwaves = groups * (uint32_t)kWavesPerGroup;
+  const uint32_t np = (n + 1u) / 2u;  // record pairs
+  uint32_t m = (uint32_t)(((uint64_t)np + 31ull * nwaves - 1u) / (31ull * nwaves));  // <= 32 pairs a run
+  if (m < kRunsPerStream) {
+    const uint32_t mr = np / nwaves;
+    m = mr < kRunsPerStream ? (mr > m ? mr : m) : kRunsPerStream;
+  }
+  if (m < 1u) m = 1u;
+  d.m = m;
+  d.K = (uint64_t)m * nwaves < np ? m * nwaves : np;
+  d.rq = np / d.K;
+  d.rr = np % d.K;
+  d.ptail = d.rq >= 3u ? kPairTailRounds : 0u;
+  d.Kst = with_claims && d.K > d.ptail * nwaves ? d.K - d.ptail * nwaves : d.K;
+  const uint32_t sets = groups / 8u;
+  d.nctr = sets >= kClaimLines ? kClaimLines : (sets > 1u ? sets : 1u);
+  d.cset = (group >> 3) % d.nctr;
+  return d;
+}
+// records [lo, hi) of run k
+__host__ __device__ inline void pair_run_bounds(const PairDeal& d, uint32_t n, uint32_t k, uint32_t& lo, uint32_t& hi) {
+  lo = 2u * (k * d.rq + (k < d.rr ? k : d.rr));
+  hi = lo + 2u * (d.rq + (k < d.rr ? 1u : 0u));
+  hi = hi < n ? hi : n;
+}
+
 struct SplitWs {
   SplitCounters* counters;
   // The other call parity's counter block: the plan kernel zeroes it for the

@@ -51,7 +51,8 @@ namespace dev {
 namespace {
 constexpr int kRing = 4;               // fixed kernel: span buffers in the prefetch ring (even)
 constexpr uint32_t kRunLg = 5;         // fixed kernel: log2(pair steps per run): runs of 64 spans
-constexpr uint32_t kRunsPerStream = 64;  // span kernel: one-task runs shrink until every stream gets this many
+// (kRunsPerStream, 64: the span and pair-run kernels' one-task runs shrink
+// until every stream gets this many -- crc32c_device.h, with the pair deal)
 // Rounds of slices / runs claimed on demand at the end of the span kernel
 // (of 16 slices per stream) and the pair-run kernel (of >= 64 runs per wave).
 // Against none, with 10 reps side by side (profiles/r05/r05l_variants_tail_confirm.json,
@@ -59,7 +60,7 @@ constexpr uint32_t kRunsPerStream = 64;  // span kernel: one-task runs shrink un
 // descriptors +3.5 %, sealed +3.0 %, 4 KiB descriptors +2.7 %; 8 / 8 rounds
 // sat between (and cost 4 KiB descriptors 2 %), 2 and 4 ran no faster.
 constexpr uint32_t kTailRounds = 12;
-constexpr uint32_t kPairTailRounds = 16;
+// (kPairTailRounds, 16: crc32c_device.h, with the pair deal)
 // The lane kernel's last rounds of runs of 64 records, claimed on demand:
 // on ~1 KB WAL records its waves left 3542-3890 us into a 3.9 ms kernel,
 // rank-1 waves 1.7 % and some XCDs 4.5 % behind the others
@@ -540,15 +541,9 @@ __global__ __launch_bounds__(kThreads) void crc32c_pair_kernel(SpanBatch a) {
   if (a.slice_start == nullptr || (a.overflow != nullptr && *a.overflow != 0u)) return;
   if ((uint32_t)const_load(a.nslices_dev, 0) != 0u || n == 0u) return;
   const uint32_t nwaves = gridDim.x * kWavesPerGroup;
-  const uint32_t np = (n + 1u) / 2u;  // record pairs
-  uint32_t m = (uint32_t)(((uint64_t)np + 31ull * nwaves - 1u) / (31ull * nwaves));  // <= 32 pairs a run
-  if (m < kRunsPerStream) {
-    const uint32_t mr = np / nwaves;
-    m = mr < kRunsPerStream ? (mr > m ? mr : m) : kRunsPerStream;
-  }
-  if (m < 1u) m = 1u;
-  const uint32_t K = (uint64_t)m * nwaves < np ? m * nwaves : np;
-  const uint32_t rq = np / K, rr = np % K;
+  // The run deal (pair_deal, crc32c_device.h: shared with the host's model).
+  const PairDeal deal = pair_deal(n, gridDim.x, blockIdx.x, a.claims != nullptr);
+  const uint32_t K = deal.K;
   if (blockIdx.x * kWavesPerGroup >= K) return;
 
   __shared__ uint32_t lds[kLdsWords];
@@ -606,12 +601,13 @@ __global__ __launch_bounds__(kThreads) void crc32c_pair_kernel(SpanBatch a) {
   // (shorter runs: no tail).  tools/check_inflight.py audits the build (a
   // claim register of its own, loop-carried, cost hipcc SGPR spills and
   // failed the audit).
-  // Eight claim counters (kClaimLines), counter c for the groups b with
-  // (b / 8) % 8 == c (each set spans every XCD and holds every SIMD rank):
-  // counter c deals the tail runs Kst + c + 8 j.
-  const uint32_t ptail = rq >= 3u ? kPairTailRounds : 0u;
-  const uint32_t Kst = a.claims != nullptr && K > ptail * nwaves ? K - ptail * nwaves : K;
-  const uint32_t cset = (blockIdx.x >> 3) & (kClaimLines - 1u);
+  // nctr claim counters (kClaimLines = 8 from 64 groups on, gridDim.x / 8
+  // below: a counter without a group would leave its runs unfolded), counter
+  // c for the groups b with (b / 8) % nctr == c (at 8: each set spans every
+  // XCD and holds every SIMD rank): counter c deals the tail runs
+  // Kst + c + nctr j.  Both wave-uniform scalars, computed once here.
+  const uint32_t Kst = deal.Kst;
+  const uint32_t nctr = rfl(deal.nctr), cset = rfl(deal.cset);
   uint32_t* const ctr = a.claims != nullptr ? a.claims + kClaimLineWords * cset : nullptr;
   auto claim_into = [&](uint32_t& e, uint32_t need) {
     uint64_t sv;
@@ -628,17 +624,13 @@ __global__ __launch_bounds__(kThreads) void crc32c_pair_kernel(SpanBatch a) {
         : "memory", "scc");
   };
   uint32_t k = wave, lo = 0, hi = 0, i = 0;
-  auto run_bounds = [&](uint32_t kk) {
-    lo = 2u * (kk * rq + (kk < rr ? kk : rr));
-    hi = lo + 2u * (rq + (kk < rr ? 1u : 0u));
-    hi = hi < n ? hi : n;
-  };
+  auto run_bounds = [&](uint32_t kk) { pair_run_bounds(deal, n, kk, lo, hi); };
   // the wave's next run after k is a claimed one
   auto wants_claim = [&]() -> bool { return Kst < K && k < K && k + nwaves >= Kst; };
   if (k >= Kst && k < K) {  // no static run: the first claim is waited for (no loads out yet)
     uint32_t got = 0;
     if (lane == 0u) got = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    k = Kst + cset + kClaimLines * rfl(got);
+    k = Kst + cset + nctr * rfl(got);
   }
   if (k < K) run_bounds(k);
   uint32_t kn = 0u;                  // the claimed successor of the current run, once read
@@ -795,7 +787,7 @@ __global__ __launch_bounds__(kThreads) void crc32c_pair_kernel(SpanBatch a) {
     for (int sl = 0; sl < 2; ++sl) {
       wait_task<kYounger>(wb[sl][0], eb[sl][0]);
       wait_task<kYounger>(wb[sl][1], eb[sl][1]);
-      if (cs[sl] != 0u) kn = Kst + cset + kClaimLines * readlane(eb[sl][1], 0);
+      if (cs[sl] != 0u) kn = Kst + cset + nctr * readlane(eb[sl][1], 0);
       if (tk[sl][0].valid())
         fold(tk[sl][0], wb[sl][0], eb[sl][0], tk[sl][1], wb[sl][1], eb[sl][1], tfirst[sl], tcnt[sl], tlast[sl] != 0u);
       if (!tk[sl ^ 1][0].valid()) goto drained;

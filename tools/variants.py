@@ -373,7 +373,7 @@ VARIANTS["slices32"] = [("crc32c_device.h", "constexpr uint32_t kSlicesPerStream
                          "constexpr uint32_t kSlicesPerStream = 32;")]
 # the span kernel's dynamic tail: rounds of slices claimed on demand
 VARIANTS["tail0"] = [("crc32c_kernels.hip", "constexpr uint32_t kTailRounds = 12;", "constexpr uint32_t kTailRounds = 0;"),
-                     ("crc32c_kernels.hip", "constexpr uint32_t kPairTailRounds = 16;",
+                     ("crc32c_device.h", "constexpr uint32_t kPairTailRounds = 16;",
                       "constexpr uint32_t kPairTailRounds = 0;")]
 VARIANTS["base_aa"] = []
 # measurement-only (wrong results): what the lane kernel's fold costs on its
@@ -613,7 +613,7 @@ VARIANTS["plan_x2"] = _plan_hoist(2)
 VARIANTS["plan_x4"] = _plan_hoist(4)
 # the pair-run kernel's claimed tail: 8 / 24 / 32 rounds (product: 16)
 for _r in (8, 24, 32):
-    VARIANTS[f"ptail{_r}"] = [("crc32c_kernels.hip", "constexpr uint32_t kPairTailRounds = 16;",
+    VARIANTS[f"ptail{_r}"] = [("crc32c_device.h", "constexpr uint32_t kPairTailRounds = 16;",
                                f"constexpr uint32_t kPairTailRounds = {_r};")]
 # the lane kernel's claimed tail on the eight claim lines (kClaimLines)
 # instead of one counter (claims still read at once)

@@ -84,6 +84,11 @@ DeviceCtx g_ctx[kMaxDevices];
 // Test hooks (read on every call: atomics, relaxed).
 // Route fixed-stride batches through the generic span kernel.
 std::atomic<bool> g_force_generic{false};
+// Test hook: bulk fixed-stride batches keep every run static (no claimed runs).
+std::atomic<bool> g_fixed_static{false};
+// This thread's last fixed-route batch: its claim counters (nullptr: a static one) and stream.
+thread_local const uint32_t* t_last_fixed_claims = nullptr;
+thread_local hipStream_t t_last_fixed_stream = nullptr;
 // Which planner-path descriptor batches go through the lane kernel first
 // (spans of kLaneMinLen..kLaneMaxLen bytes; the rest follow on the generic
 // path): 0 = log-record batches (PRISMDB_CRC32C_LOG_HEADER), 1 = all, -1 = none.
@@ -627,8 +632,36 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
       a.len_c >= 4 && a.len_c <= max_len && (a.len_c & 3u) == 0 &&
       (a.stride & 3u) == 0 && (reinterpret_cast<uintptr_t>(a.base) & 3u) == 0 &&
       !g_force_generic.load(std::memory_order_relaxed)) {
+    // A bulk batch (full runs for every wave) claims its runs on demand: the
+    // counters are the stream workspace's block of this call's parity, zero
+    // since the call before zeroed it, and the kernel zeroes the other block
+    // for the call after -- the planner path's scheme, no fill in front.
+    // Smaller batches (one SST file, a pipeline chunk) take no workspace.
+    Workspace* w = nullptr;
+    if (prismdb::dev::fixed_claims(a.n, (uint32_t)groups) && (a.n >> 37) == 0 &&
+        !g_fixed_static.load(std::memory_order_relaxed)) {
+      int rc = 0;
+      if ((w = FindWorkspace(s, rc)) == nullptr) return rc;
+      char* const cb = reinterpret_cast<char*>(w->ws.counters);
+      if (w->dirty) {  // the last call failed after using this block, before its plan kernel
+        hipError_t e = hipMemsetAsync(cb + prismdb::dev::kCounterBlock * (w->pcall & 1u), 0, prismdb::dev::kCounterBlock, s);
+        if (e != hipSuccess) return FailHip(e, "hipMemsetAsync");
+        w->dirty = false;
+      }
+      a.claims = reinterpret_cast<uint32_t*>(cb + prismdb::dev::kCounterBlock * (w->pcall & 1u) + 256);
+      a.zero_next = reinterpret_cast<uint32_t*>(cb + prismdb::dev::kCounterBlock * ((w->pcall + 1u) & 1u));
+      t_last_fixed_claims = a.claims;
+      t_last_fixed_stream = s;
+    } else {
+      t_last_fixed_claims = nullptr;
+    }
     hipError_t e = prismdb::dev::launch_fixed(a, verify, groups, s);
-    return e == hipSuccess ? 0 : FailHip(e, "fixed kernel launch");
+    if (e != hipSuccess) return FailHip(e, "fixed kernel launch");  // (not run: its block is still zero)
+    if (w != nullptr) {
+      w->pcall++;  // the next call's block is the one this kernel zeroes
+      (void)hipEventRecord(w->done[w->gen & 1u], s);  // the workspace is in use until here
+    }
+    return 0;
   }
   int rc = 0;
   Workspace* w = FindWorkspace(s, rc);
@@ -1029,6 +1062,29 @@ int prismdb_test_hooks_enabled(void) { return prismdb::TestHooksEnabled() ? 1 : 
 // fixed-stride batches through the generic span kernel too;
 void prismdb_crc32c_force_generic(int on) {
   if (prismdb::TestHooksEnabled()) g_force_generic.store(on != 0, std::memory_order_relaxed);
+}
+
+// bulk fixed-stride batches with every run dealt statically (no claimed
+// runs, no workspace): the kernel as it was before it claimed;
+void prismdb_crc32c_fixed_static(int on) {
+  if (prismdb::TestHooksEnabled()) g_fixed_static.store(on != 0, std::memory_order_relaxed);
+}
+
+// the claims of this thread's last fixed-route batch, summed over its
+// counters: the runs claimed plus one failed claim per wave.  Returns 0 (and
+// *out = 0) after a static batch, -1 before any or on an error.  Call it
+// before the stream's next batch: that one zeroes the block.
+int prismdb_crc32c_last_fixed_claims(uint64_t* out) {
+  if (!prismdb::TestHooksEnabled() || out == nullptr) return -1;
+  *out = 0;
+  if (t_last_fixed_claims == nullptr) return 0;
+  namespace d = prismdb::dev;
+  uint32_t blk[d::kClaimLines * d::kClaimLineWords];
+  hipError_t e = hipStreamSynchronize(t_last_fixed_stream);
+  if (e == hipSuccess) e = hipMemcpy(blk, t_last_fixed_claims, sizeof(blk), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return FailHip(e, "prismdb_crc32c_last_fixed_claims");
+  for (uint32_t j = 0; j < d::kClaimLines; ++j) *out += blk[d::kClaimLineWords * j];
+  return 0;
 }
 
 // which planner-path descriptor batches take the lane kernel first (0 =

@@ -107,6 +107,10 @@ struct SpanBatch {
   // nullable, zero at launch: the pair-run kernel's kClaimLines claim
   // counters, one per 128-B line (word kClaimLineWords * j)
   uint32_t* claims;
+  // nullable: the fixed kernel's claiming launches (no plan kernel in front)
+  // zero the workspace's other counter block, as the plan kernel does
+  // (SplitWs::zero_next)
+  uint32_t* zero_next;
 };
 
 // Below this many spans the pair-run kernel's extra launch (~5 us) costs more
@@ -180,6 +184,43 @@ __host__ __device__ inline void pair_run_bounds(const PairDeal& d, uint32_t n, u
   lo = 2u * (k * d.rq + (k < d.rr ? k : d.rr));
   hi = lo + 2u * (d.rq + (k < d.rr ? 1u : 0u));
   hi = hi < n ? hi : n;
+}
+
+// The fixed kernel's run deal (crc32c_fixed_kernel; its comment has the
+// measurements), shared with the host, which gives a launch claim counters
+// only when the deal uses them.  Runs of 2 << lg spans (64, shortened for
+// batches too small to give every wave four full runs), NR of them; run k is
+// spans [k << (lg + 1), +run).  Full runs, with_claims: the first
+// kFixedStaticEighths / 8 of a wave's rounds are dealt statically (wave w:
+// w, w + nwaves, ... below Kst), runs Kst..NR-1 are claimed on demand from
+// the pair deal's counters (counter c: Kst + c + nctr * j for its j-th
+// claim).  Otherwise Kst = NR: every run static, no atomics.
+constexpr uint32_t kFixedRunLg = 5;          // log2(pair steps per run): runs of 64 spans
+constexpr uint32_t kFixedStaticEighths = 0;  // of a wave's rounds, dealt statically before it claims
+struct FixedDeal {
+  uint32_t lg;
+  uint64_t NR, Kst;
+  uint32_t nctr, cset;
+};
+__host__ __device__ inline FixedDeal fixed_deal(uint64_t n, uint32_t groups, uint32_t group, bool with_claims) {
+  FixedDeal d;
+  const uint64_t nwaves = (uint64_t)groups * (uint32_t)kWavesPerGroup;
+  d.lg = kFixedRunLg;
+  while (d.lg > 0 && (n >> (d.lg + 1)) < nwaves * 4u) --d.lg;
+  d.NR = (n + (2ull << d.lg) - 1u) >> (d.lg + 1);
+  d.Kst = d.NR;
+  if (with_claims && d.lg == kFixedRunLg) {
+    const uint64_t rounds = (d.NR + nwaves - 1u) / nwaves;
+    d.Kst = rounds * kFixedStaticEighths / 8u * nwaves;  // (< NR: rounds >= 4, eighths < 8)
+  }
+  const uint32_t sets = groups / 8u;  // (as pair_deal: every counter has a group)
+  d.nctr = sets >= kClaimLines ? kClaimLines : (sets > 1u ? sets : 1u);
+  d.cset = (group >> 3) % d.nctr;
+  return d;
+}
+// whether a fixed batch of n spans on this grid claims runs (the host's test)
+__host__ __device__ inline bool fixed_claims(uint64_t n, uint32_t groups) {
+  return (n >> (kFixedRunLg + 1)) >= (uint64_t)groups * (uint32_t)kWavesPerGroup * 4u;
 }
 
 struct SplitWs {

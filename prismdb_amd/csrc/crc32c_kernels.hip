@@ -50,7 +50,7 @@ namespace prismdb {
 namespace dev {
 namespace {
 constexpr int kRing = 4;               // fixed kernel: span buffers in the prefetch ring (even)
-constexpr uint32_t kRunLg = 5;         // fixed kernel: log2(pair steps per run): runs of 64 spans
+// (kFixedRunLg, 5: crc32c_device.h, with the fixed deal: runs of 64 spans)
 // (kRunsPerStream, 64: the span and pair-run kernels' one-task runs shrink
 // until every stream gets this many -- crc32c_device.h, with the pair deal)
 // Rounds of slices / runs claimed on demand at the end of the span kernel
@@ -839,19 +839,65 @@ __global__ __launch_bounds__(kThreads) void crc32c_fixed_kernel(SpanBatch a) {
   // spans dealt one by one.)
   // kRun = 64, shortened (power of two >= 2) for batches too small to give
   // every wave a few full runs.
-  static_assert(kRunLg <= 5, "a run's results fit the 64 lanes");
-  uint32_t lg = kRunLg;  // log2(pair steps per run)
-  while (lg > 0 && (n >> (lg + 1)) < nwaves * 4u) --lg;
+  static_assert(kFixedRunLg <= 5, "a run's results fit the 64 lanes");
+  // The run deal (fixed_deal, crc32c_device.h: shared with the host).
+  const FixedDeal deal = fixed_deal(n, gridDim.x, blockIdx.x, a.claims != nullptr);
+  const uint32_t lg = deal.lg;  // log2(pair steps per run)
   const uint64_t kRun = 2ull << lg;
-  // First span of the wave's next pair step: +2 inside a run, then on to the
-  // wave's next run (the other waves' runs in between).
+  // Claimed runs.  With every wave's 64 runs dealt statically, a 16 Mi x 4 KiB
+  // batch's waves left over 5.2-10.6 ms by SIMD age rank and XCD, and the
+  // youngest waves alone read at 40-75 % of the steady rate for the last
+  // millisecond (tools/wave_timeline.py --work fixed, profiles/r07/).  So a
+  // bulk batch (full runs) deals only runs k < Kst statically and the waves
+  // claim the rest in rising order from the pair-run kernel's counters
+  // (counter c: runs Kst + c + nctr j), the streams still sweeping the batch
+  // front to back.  As there, a claim goes out one run ahead -- after the
+  // loads of the first pair of the run before -- and is read behind that ring
+  // slot's next counted wait, which retires it: no wave waits for a claim.
+  // It returns into lane 0 of a register of its own (a 4 KiB span leaves no
+  // padding lane in the ring).  A wave's failed claim (a run >= NR) ends it.
+  // Small batches (shortened runs) and launches without counters: Kst = NR,
+  // every run static, no atomics.
+  const uint64_t NR = deal.NR, Kst = deal.Kst;
+  const bool claiming = Kst < NR;
+  const uint32_t nctr = rfl(deal.nctr), cset = rfl(deal.cset);
+  uint32_t* const ctr = claiming ? a.claims + kClaimLineWords * cset : nullptr;
+  // the workspace's other counter block, for the stream's next call (the plan kernel's job on its path)
+  if (blockIdx.x == 0u && a.zero_next != nullptr) {
+    if (tid < 64u) a.zero_next[tid] = 0u;
+    else if (tid < 64u + kClaimLines) a.zero_next[64u + kClaimLineWords * (tid - 64u)] = 0u;
+  }
+  auto claim_into = [&](uint32_t& e, uint32_t need) {
+    uint64_t sv;
+    asm volatile(
+        "s_cmp_eq_u32 %2, 0\n\t"
+        "s_cbranch_scc1 .Lno_fclaim%=\n\t"
+        "s_mov_b64 %1, exec\n\t"
+        "s_mov_b64 exec, 1\n\t"
+        "global_atomic_add %0, %3, %4, %5 sc0\n\t"
+        "s_mov_b64 exec, %1\n"
+        ".Lno_fclaim%=:"
+        : "+v"(e), "=&s"(sv)
+        : "s"(need), "v"(0u), "v"(1u), "s"(ctr)
+        : "memory", "scc");
+  };
+  // the successor of run k is a claimed one
+  auto claimed_next = [&](uint64_t k) -> bool { return claiming && k < NR && k + nwaves >= Kst; };
   // (Pairing spans half a run apart instead cost 3.7 %,
   // profiles/r02af_variants_fixed_far_pair.json.)
   const uint64_t kSecond = 1u;
-  const uint64_t jump = (nwaves - 1u) * kRun + 2u;
-  auto adv = [&](uint64_t x) -> uint64_t { return ((x + 2u) & (kRun - 1u)) ? x + 2u : x + jump; };
-  uint64_t cur = wave * kRun;  // first span of the pair being folded
+  uint64_t arun = wave;  // the run of the next pair to issue
+  if (claiming && arun >= Kst) {  // no static run: the first claim is waited for (no loads out yet)
+    uint32_t got = 0;
+    if (lane == 0u) got = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    arun = Kst + cset + (uint64_t)nctr * rfl(got);
+  }
+  uint64_t crun = arun;        // the run being folded
+  uint64_t cur = arun * kRun;  // first span of the pair being folded
   if (cur >= n) return;
+  uint32_t cl[kRing / 2] = {};  // per ring pair, lane 0: the return of the claim issued behind its loads
+  uint64_t kn = 0u;  // the claimed successor of arun, once read
+  uint32_t need = claimed_next(arun) ? 1u : 0u;  // claim after the next pair's loads
 
   // pk: leading zero words (round 0).  Verify sizes K for len + 4, so pk >= 1
   // and lane 0 of round 0 -- padding, masked out of the fold -- loads the
@@ -924,11 +970,26 @@ __global__ __launch_bounds__(kThreads) void crc32c_fixed_kernel(SpanBatch a) {
   static_assert(kYounger <= 63, "vmcnt is a 6-bit counter");
   uint32_t ring[kRing][kRounds];
   uint64_t ahead = cur;  // first span of the next pair to issue
+  // +2 inside a run, then on to the wave's next run (the other waves' runs in
+  // between): the next static one, or the one claimed while this one was read
+  auto adv_ahead = [&]() {
+    if ((ahead + 2u) & (kRun - 1u)) {
+      ahead += 2u;
+    } else {
+      arun = claimed_next(arun) ? kn : arun + nwaves;
+      ahead = arun * kRun;
+      need = claimed_next(arun) ? 1u : 0u;
+    }
+  };
+  uint32_t cs[kRing / 2];  // per ring pair: a claim went out behind its loads
 #pragma unroll
   for (int d = 0; d < kRing; d += 2) {
     issue(ahead, ring[d]);
     issue(ahead + kSecond, ring[d + 1]);
-    ahead = adv(ahead);
+    cs[d / 2] = rfl(need);  // (rfl: an SGPR operand -- hipcc takes the flag for divergent)
+    claim_into(cl[d / 2], cs[d / 2]);
+    need = 0u;
+    adv_ahead();
   }
   // One exit, at the bottom of a whole ring turn: steps past the wave's last
   // pair (their loads re-read span n-1) are waited for but not folded.  The
@@ -939,19 +1000,33 @@ __global__ __launch_bounds__(kThreads) void crc32c_fixed_kernel(SpanBatch a) {
 #pragma unroll
     for (int s = 0; s < kRing; s += 2) {
       wait2(ring[s], ring[s + 1]);
-      const uint64_t nxt = adv(cur);
+      asm volatile("" : "+v"(cl[s / 2]));  // (a claim issued behind this pair's loads has landed)
+      if (cs[s / 2] != 0u) kn = Kst + cset + (uint64_t)nctr * readlane(cl[s / 2], 0);
+      const bool run_end = ((cur + 2u) & (kRun - 1u)) == 0;
       if (cur < n) {
         fold2(ring[s], ring[s + 1]);
-        if (nxt >= n || (nxt & (kRun - 1u)) == 0) flush();
+        if (run_end || cur + 2u >= n) flush();
       }
-      cur = nxt;
+      // on to the wave's next run: a claimed one is the run `ahead` is in
+      // (full runs: 32 pair steps, the ring runs two ahead)
+      if (run_end) {
+        crun = claimed_next(crun) ? arun : crun + nwaves;
+        cur = crun * kRun;
+      } else {
+        cur += 2u;
+      }
       issue(ahead, ring[s]);
       issue(ahead + kSecond, ring[s + 1]);
-      ahead = adv(ahead);
+      cs[s / 2] = rfl(need);
+      claim_into(cl[s / 2], cs[s / 2]);
+      need = 0u;
+      adv_ahead();
     }
     if (cur >= n) break;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int d = 0; d < kRing / 2; ++d) asm volatile("" : "+v"(cl[d]));
 #pragma unroll
   for (int d = 0; d < kRing; ++d) {
 #pragma unroll

@@ -328,14 +328,23 @@ SETPRIO = (
     "          else __builtin_amdgcn_s_setprio(3);\n")
 VARIANTS["fixed_rot"] = [
     ("crc32c_kernels.hip",
-     "  uint64_t cur = wave * kRun;  // first span of the pair being folded\n  if (cur >= n) return;\n",
-     "  uint64_t cur = wave * kRun;  // first span of the pair being folded\n  if (cur >= n) return;\n"
+     "  uint64_t cur = arun * kRun;  // first span of the pair being folded\n  if (cur >= n) return;\n",
+     "  uint64_t cur = arun * kRun;  // first span of the pair being folded\n  if (cur >= n) return;\n"
      "  uint32_t rot = rfl((tid >> 6) >> 2);\n  {\n" + SETPRIO + "  }\n"),
     ("crc32c_kernels.hip",
-     "        if (nxt >= n || (nxt & (kRun - 1u)) == 0) flush();\n",
-     "        if (nxt >= n || (nxt & (kRun - 1u)) == 0) {\n          flush();\n          rot = (rot + 1u) & 3u;\n"
+     "        if (run_end || cur + 2u >= n) flush();\n",
+     "        if (run_end || cur + 2u >= n) {\n          flush();\n          rot = (rot + 1u) & 3u;\n"
      + SETPRIO + "        }\n"),
 ]
+# the fixed kernel with every run static (the kernel before it claimed runs),
+# and with half / seven eighths of a wave's rounds static before it claims
+VARIANTS["fixed_static"] = [("crc32c_capi.hip", "std::atomic<bool> g_fixed_static{false};",
+                             "std::atomic<bool> g_fixed_static{true};")]
+VARIANTS["fixed_static2"] = VARIANTS["fixed_static"]  # (A/A)
+VARIANTS["fixed_st4"] = [("crc32c_device.h", "constexpr uint32_t kFixedStaticEighths = 0;",
+                          "constexpr uint32_t kFixedStaticEighths = 4;")]
+VARIANTS["fixed_st7"] = [("crc32c_device.h", "constexpr uint32_t kFixedStaticEighths = 0;",
+                          "constexpr uint32_t kFixedStaticEighths = 7;")]
 # measurement: the fixed kernel's per-wave entry and exit (tools/wave_timeline.py --work fixed)
 VARIANTS["fixed_ts"] = [
     ("crc32c_kernels.hip",
@@ -349,6 +358,22 @@ VARIANTS["fixed_ts"] = [
      "    const uint64_t ts1 = __builtin_amdgcn_s_memrealtime();\n"
      "    reinterpret_cast<uint64_t*>(a.out + ((n + 3u) & ~3ull))[2u * wave + lane] = lane == 0u ? ts0 : ts1;\n"
      "  }\n}\n"),
+    # ... and every run's start (the wave's previous run end, or its entry) and
+    # end, two stamps per run behind the waves' (one 16-B store per 64 spans)
+    ("crc32c_kernels.hip",
+     "  uint32_t res = 0, bad = 0;\n  // Two spans folded together: two independent LDS dependency chains per wave.\n",
+     "  uint32_t res = 0, bad = 0;\n  uint64_t tsr = ts0;\n"
+     "  // Two spans folded together: two independent LDS dependency chains per wave.\n"),
+    ("crc32c_kernels.hip",
+     "    const uint32_t last = (uint32_t)(cur & (kRun - 1u)) + 1u;\n",
+     "    const uint32_t last = (uint32_t)(cur & (kRun - 1u)) + 1u;\n"
+     "    if (a.out != nullptr && n >= (1u << 20)) {  // (a bulk batch: full runs)\n"
+     "      const uint64_t ts1 = __builtin_amdgcn_s_memrealtime();\n"
+     "      if (lane < 2u)\n"
+     "        reinterpret_cast<uint64_t*>(a.out + ((n + 3u) & ~3ull))[2u * nwaves + 2u * (b0 >> (lg + 1u)) + lane] =\n"
+     "            lane == 0u ? tsr : ts1;\n"
+     "      tsr = ts1;\n"
+     "    }\n"),
 ] + MEASURE_ONLY
 # measurement: the span kernel's per-wave entry and exit (tools/wave_timeline.py --work mixed)
 VARIANTS["span_ts"] = [
@@ -381,6 +406,7 @@ VARIANTS["base_aa"] = []
 VARIANTS["lane_nofold"] = [("crc32c_kernels.hip", "      for (int i = 0; i < 32; ++i) y = step256(lds, tab, y, w[i >> 2][i & 3]);\n",
                             "      for (int i = 0; i < 32; ++i) y ^= w[i >> 2][i & 3];\n")] + MEASURE_ONLY
 VARIANTS["fixed_ts_rot"] = VARIANTS["fixed_ts"] + VARIANTS["fixed_rot"]
+VARIANTS["fixed_ts_static"] = VARIANTS["fixed_ts"] + VARIANTS["fixed_static"]
 # measurement-only (wrong results): the lane kernel's side loads with every
 # lane reading the wave's zero region -- what the remaining ones cost
 VARIANTS["lane_sidezero"] = [

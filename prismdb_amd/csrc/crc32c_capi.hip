@@ -23,6 +23,7 @@
 #include "../../include/prismdb_crc32c.h"
 #include "crc32c_device.h"
 #include "crc32c_gf2.h"
+#include "crc32c_route.h"
 
 namespace prismdb {
 // Streams the engine creates for itself (pipeline rings, batch_multi
@@ -37,27 +38,32 @@ using prismdb::dev::DeviceTables;
 using prismdb::dev::SpanBatch;
 using prismdb::dev::SplitCounters;
 using prismdb::dev::SplitWs;
+using prismdb::route::Forced;
+using prismdb::route::kRouteAuto;
+using prismdb::route::kRouteDirect;
+using prismdb::route::kRoutePlanner;
+using prismdb::route::Route;
 
 thread_local std::string t_last_error;
-// The calling thread's last descriptor batch: its split counters and stream
-// (read back only by the test hook prismdb_crc32c_last_split).
-thread_local const prismdb::dev::SplitCounters* t_last_counters = nullptr;
-thread_local hipStream_t t_last_stream = nullptr;
-thread_local bool t_last_direct = false;
-thread_local bool t_last_pair = false;  // the planner batch launched the pair-run kernel
-thread_local const uint32_t* t_last_stats = nullptr;
-// Whether that batch ran on an engine-owned stream (a pipeline ring, a clique
-// stream), whose workspace any thread may release (ReleaseEngineStream), and
-// the release epoch then: the hooks above refuse to read it after a release.
-thread_local bool t_last_owned = false;
-thread_local uint64_t t_last_epoch = 0;
 std::atomic<uint64_t> g_release_epoch{0};
-
-// The calling thread's last batch ran on an engine stream whose workspace
-// has been released since (by any thread): its pointers are gone.
-bool LastBatchStale() {
-  return t_last_owned && t_last_epoch != g_release_epoch.load(std::memory_order_acquire);
-}
+// The calling thread's last batch, for the read-back test hooks
+// (prismdb_crc32c_last_*, _direct_stats): written once per batch by the route
+// that ran it, before its launch.  A hook answers for its own kind of batch.
+enum LastRoute { kLastNone, kLastFixedStatic, kLastFixedClaims, kLastOneLaunch, kLastPlanner };
+struct LastBatch {
+  LastRoute route = kLastNone;
+  hipStream_t stream = nullptr;
+  const char* counters = nullptr;   // planner, fixed-claims: the call's counter block (nullptr: released)
+  const uint32_t* stats = nullptr;  // one-launch: the workspace's usage counters (nullptr: released)
+  bool pair = false;                // planner: the pair-run kernel was launched
+  // Whether the batch's workspace is an engine-owned stream's (a pipeline
+  // ring, a clique stream), which any thread may release
+  // (ReleaseEngineStream), and the release epoch then: the hooks refuse to
+  // read it after a release.
+  bool owned = false;
+  uint64_t epoch = 0;
+};
+thread_local LastBatch t_last;
 
 int Fail(int code, const std::string& msg) {
   t_last_error = msg;
@@ -81,39 +87,25 @@ struct DeviceCtx {
 
 DeviceCtx g_ctx[kMaxDevices];
 
-// Test hooks (read on every call: atomics, relaxed).
+// Test hooks (read on every call: atomics, relaxed).  The first five are the
+// routing rule's knobs (route::Knobs: route_of in crc32c_route.h says what
+// each does, with the measurements behind the defaults).
 // Route fixed-stride batches through the generic span kernel.
 std::atomic<bool> g_force_generic{false};
 // Test hook: bulk fixed-stride batches keep every run static (no claimed runs).
 std::atomic<bool> g_fixed_static{false};
-// This thread's last fixed-route batch: its claim counters (nullptr: a static one) and stream.
-thread_local const uint32_t* t_last_fixed_claims = nullptr;
-thread_local hipStream_t t_last_fixed_stream = nullptr;
 // Which planner-path descriptor batches go through the lane kernel first
 // (spans of kLaneMinLen..kLaneMaxLen bytes; the rest follow on the generic
 // path): 0 = log-record batches (PRISMDB_CRC32C_LOG_HEADER), 1 = all, -1 = none.
 std::atomic<int> g_lane_mode{0};
 // Descriptor batches of at most this many spans take the one-launch kernel.
 std::atomic<uint64_t> g_direct_max{prismdb::dev::kDirectPlainSpans};
+// Descriptor batches of more than g_direct_max spans: 1 windows, 0 planner, 2 by shape.
+std::atomic<int> g_windows{2};
 // The one-launch path's ticket capacity (tests shrink it to reach the
 // whole-span fallback) and its debug flags (DirectWs::dbg).
 std::atomic<uint32_t> g_direct_cap{prismdb::dev::kDirectTickets};
 std::atomic<uint32_t> g_direct_dbg{0};
-// Descriptor batches of more than g_direct_max spans (without LOG_HEADER):
-// windows of the one-launch kernel (1), the planner path (0), or (2, the
-// default) windows up to two of them for batches that seal or verify block
-// trailers (RunBatch), the planner path otherwise and beyond.  Two
-// windows of SST files (twelve files, 201 744 spans) take 13.4 us per file,
-// against 21.6 on the planner path, whose 5-7 launches and segment pass cost
-// ~120 us per call; from there on the planner's balance wins, and on mixed
-// span sizes it wins at any size (profiles/r04/r04h_bench.json,
-// r04h_configs.json).  The one-launch kernel deals each wave a static run
-// of consecutive spans, and a group leaves its CU only when its slowest wave
-// is done: on spans of mixed sizes the windows lose to the planner's
-// task-balanced slices (config-3 mix 65.7 against 74.8 % of the roofline,
-// random spans 70.3 against 77.1 %), on uniform SST spans they win (72.8
-// against 70.8 %; profiles/r04/r04e_configs.json).
-std::atomic<int> g_windows{2};
 // The grid of the persistent kernels, in workgroups: 0 (the default) = the
 // device's CU count, else min(this, the CU count) -- never more, the kernels'
 // groups are all co-resident.  The tests run every route at reduced grids:
@@ -126,6 +118,12 @@ std::atomic<int> g_grid{0};
 int Groups(int cus) {
   const int g = g_grid.load(std::memory_order_relaxed);
   return g > 0 && g < cus ? g : cus;
+}
+
+prismdb::route::Knobs ReadKnobs() {
+  const auto rx = std::memory_order_relaxed;
+  return {g_force_generic.load(rx), g_fixed_static.load(rx), g_lane_mode.load(rx), g_direct_max.load(rx),
+          g_windows.load(rx)};
 }
 
 void BuildTables(DeviceTables* t) {
@@ -159,7 +157,7 @@ void BuildTables(DeviceTables* t) {
   }
 }
 
-int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify, hipStream_t s, int route);
+int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify, hipStream_t s, Forced forced);
 
 // Device known-answer self-test (util/crc32c.cc:269-273 vector, plus a 4 KiB
 // block and a > kLongSpan span checked against the host Extend), through both
@@ -210,7 +208,7 @@ int SelfTest(DeviceCtx& ctx) {
     uint32_t got[3] = {0, 0, 0};
     e = hipMemset(d_out, 0, sizeof(got));
     if (e != hipSuccess) rc = FailHip(e, "self-test memset");
-    if (rc == 0) rc = RunBatch(ctx, a, true, false, nullptr, route);
+    if (rc == 0) rc = RunBatch(ctx, a, true, false, nullptr, route == 1 ? kRouteDirect : kRoutePlanner);
     if (rc == 0) {
       e = hipStreamSynchronize(nullptr);
       if (e != hipSuccess) rc = FailHip(e, "self-test sync");
@@ -320,12 +318,12 @@ constexpr size_t kMaxWorkspaces = 8;
 // device-wide), free every block on the device's release stream, and trim
 // the default pool so the memory leaves the process's pool too.
 void SyncAndRelease(Workspace& w) {
-  {
-    const char* t = reinterpret_cast<const char*>(t_last_counters);
-    const char* c = reinterpret_cast<const char*>(w.ws.counters);
-    if (c != nullptr && t >= c && t < c + 2 * prismdb::dev::kCounterBlock) t_last_counters = nullptr;
-  }
-  if (w.direct != nullptr && t_last_stats == reinterpret_cast<const uint32_t*>(w.direct + 32)) t_last_stats = nullptr;
+  // the releasing thread's last-batch record forgets what lies in w (other
+  // threads': g_release_epoch)
+  const char* c = reinterpret_cast<const char*>(w.ws.counters);
+  if (c != nullptr && t_last.counters >= c && t_last.counters < c + 2 * prismdb::dev::kCounterBlock)
+    t_last.counters = nullptr;
+  if (w.direct != nullptr && t_last.stats == reinterpret_cast<const uint32_t*>(w.direct + 32)) t_last.stats = nullptr;
   int cur = 0;
   (void)hipGetDevice(&cur);
   if (w.device != cur) (void)hipSetDevice(w.device);
@@ -570,7 +568,21 @@ int DirectWorkspace(Workspace& w, hipStream_t s, prismdb::dev::DirectWs* out) {
   return 0;
 }
 
-enum Route { kRouteAuto = 0, kRouteDirect = 1, kRoutePlanner = 2 };
+// Spans [at, at + m) of a batch, as a batch of their own.
+SpanBatch Slice(const SpanBatch& a, bool desc, uint64_t at, uint64_t m) {
+  SpanBatch p = a;
+  p.n = m;
+  if (desc) {
+    p.off += at;
+    p.len += at;
+    if (p.init != nullptr) p.init += at;
+  } else {
+    p.base += at * a.stride;
+  }
+  if (p.out != nullptr) p.out += at;
+  if (p.mismatch != nullptr) p.mismatch += at;
+  return p;
+}
 
 // A descriptor batch of more spans than one launch of the one-launch kernel
 // takes, as ceil(n / wmax) equal windows of consecutive spans, one launch of
@@ -581,30 +593,93 @@ enum Route { kRouteAuto = 0, kRouteDirect = 1, kRoutePlanner = 2 };
 // the CUs: twelve SST files per call took 18.0 us per file that way against
 // 12.8 us in calls of seven files, profiles/r04/r04g_bench.json.)
 int RunWindows(DeviceCtx& ctx, const SpanBatch& a, bool verify, hipStream_t s, uint64_t wmax) {
-  const uint64_t cap = 64ull * (uint64_t)Groups(ctx.cus) * (prismdb::dev::kDirectThreads / 64);  // one span run per wave
-  if (wmax > cap) wmax = cap;
   const uint64_t nwin = (a.n + wmax - 1) / wmax;
   uint64_t at = 0;
   for (uint64_t k = 0; k < nwin; ++k) {
     const uint64_t m = (a.n - at) / (nwin - k);  // equal windows, the remainder spread over the last ones
-    SpanBatch p = a;
-    p.off += at;
-    p.len += at;
-    if (p.init != nullptr) p.init += at;
-    if (p.out != nullptr) p.out += at;
-    if (p.mismatch != nullptr) p.mismatch += at;
-    p.n = m;
-    if (int rc = RunBatch(ctx, p, true, verify, s, kRouteDirect)) return rc;
+    if (int rc = RunBatch(ctx, Slice(a, true, at, m), true, verify, s, kRouteDirect)) return rc;
     at += m;
   }
   return 0;
 }
 
-// Launch sequence.  Fixed stride, aligned, <= 4 KiB: one kernel.  Descriptor
-// batches of <= g_direct_max spans: one kernel (crc32c_direct.hip).  The
-// rest: plan (span records, long spans cut into segments) -> span pass (long
-// spans skipped) -> segment pass -> combine, with the lane kernel and its
-// list in front for log-record batches.
+// The span kernel indexes records with 32 bits: larger batches in pieces.
+int RunCut(DeviceCtx& ctx, const SpanBatch& a, bool desc, bool verify, hipStream_t s) {
+  const uint64_t kMax = prismdb::dev::kMaxGenericSpans;
+  for (uint64_t i = 0; i < a.n; i += kMax)
+    if (int rc = RunBatch(ctx, Slice(a, desc, i, a.n - i < kMax ? a.n - i : kMax), desc, verify, s, kRoutePlanner))
+      return rc;
+  return 0;
+}
+
+// A workspace's two counter blocks, by call parity (pcall): this call's --
+// zero, since the call before zeroed it (its plan kernel or its claiming
+// fixed kernel: no fill kernel in front of the call; it and its gap took
+// 6.7 us of a config-5 call, profiles/r05/r05aa_c5_seal/one_call_timeline.csv)
+// or the workspace is new -- and the next call's, which this call's kernel
+// zeroes.  dirty (a call used its block and failed before that kernel was
+// enqueued): the block is filled here first.  The caller does w.pcall++ once
+// the kernel is enqueued.
+struct CounterBlocks { char *cur, *next; };
+int TakeCounterBlocks(Workspace& w, hipStream_t s, CounterBlocks* out) {
+  static_assert(sizeof(SplitCounters) <= 256, "SplitCounters fills the first 256 B of a counter block");
+  char* const cb = reinterpret_cast<char*>(w.ws.counters);
+  out->cur = cb + prismdb::dev::kCounterBlock * (w.pcall & 1u);
+  out->next = cb + prismdb::dev::kCounterBlock * ((w.pcall + 1u) & 1u);
+  if (w.dirty) {
+    hipError_t e = hipMemsetAsync(out->cur, 0, prismdb::dev::kCounterBlock, s);
+    if (e != hipSuccess) return FailHip(e, "hipMemsetAsync");
+    w.dirty = false;
+  }
+  return 0;
+}
+
+// One kernel.  A claiming batch takes the stream workspace's counter block
+// (behind its 256 B of split counters) -- the planner path's scheme.
+int RunFixed(SpanBatch& a, bool verify, int groups, bool claims, hipStream_t s) {
+  Workspace* w = nullptr;
+  t_last = {kLastFixedStatic, s};
+  if (claims) {
+    int rc = 0;
+    if ((w = FindWorkspace(s, rc)) == nullptr) return rc;
+    CounterBlocks cb{};
+    if ((rc = TakeCounterBlocks(*w, s, &cb)) != 0) return rc;
+    a.claims = reinterpret_cast<uint32_t*>(cb.cur + 256);
+    a.zero_next = reinterpret_cast<uint32_t*>(cb.next);
+    t_last = {kLastFixedClaims, s, cb.cur, nullptr, false, w->owned, g_release_epoch.load(std::memory_order_acquire)};
+  }
+  hipError_t e = prismdb::dev::launch_fixed(a, verify, groups, s);
+  if (e != hipSuccess) return FailHip(e, "fixed kernel launch");  // (not run: its block is still zero)
+  if (w != nullptr) {
+    w->pcall++;  // the next call's block is the one this kernel zeroes
+    (void)hipEventRecord(w->done[w->gen & 1u], s);  // the workspace is in use until here
+  }
+  return 0;
+}
+
+// Whatever a route on a workspace does, the workspace's events mark the end
+// of the call's work: the last kernel's own completion (its stop event:
+// by_launch), or else a marker recorded when RunBatch returns (ordered: it
+// covers everything before it).
+struct MarkDone {
+  Workspace* w;
+  hipStream_t s;
+  bool by_launch = false;
+  ~MarkDone() {
+    if (!by_launch) (void)hipEventRecord(w->done[w->gen & 1u], s);
+  }
+};
+
+// One launch of the one-launch kernel (crc32c_direct.hip).
+int RunDirect(const SpanBatch& a, bool verify, int groups, Workspace* w, hipStream_t s, MarkDone& mark) {
+  prismdb::dev::DirectWs d{};
+  if (int rc = DirectWorkspace(*w, s, &d)) return rc;
+  t_last = {kLastOneLaunch, s, nullptr, d.stats, false, w->owned, g_release_epoch.load(std::memory_order_acquire)};
+  mark.by_launch = true;
+  hipError_t e = prismdb::dev::launch_direct(a, verify, groups, d, s, w->done[w->gen & 1u]);
+  return e == hipSuccess ? 0 : FailHip(e, "direct kernel launch");
+}
+
 // The workspace's side stream and its fork / join events, created on first use.
 int SideStream(Workspace* w) {
   if (w->side != nullptr) return 0;
@@ -614,74 +689,17 @@ int SideStream(Workspace* w) {
   return e == hipSuccess ? 0 : FailHip(e, "side stream");
 }
 
-int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify, hipStream_t s, int route) {
-  SpanBatch a = base_args;
-  const int groups = Groups(ctx.cus);  // read once: this call's grids and its arithmetic on them
-  // PRISMDB_CRC32C_UNORDERED is accepted and has no effect: every launch is
-  // in stream order (an any-order launch is not supported on gfx9, and it
-  // measured slower where it ran: 25.9 against 24.9 us per SST file)
-  a.flags &= ~PRISMDB_CRC32C_UNORDERED;
-  a.tabs = ctx.tabs;
-  a.role = prismdb::dev::kRoleSpans;
-  // Fast path: fixed stride, 4-byte aligned, 4..4096-byte multiple-of-4 spans
-  // (verify: up to 4092 bytes and not a multiple of 256, so that the stored
-  // trailer word fits round 0's padding lanes).
-  const uint32_t max_len = 4u * prismdb::dev::kChunkWords - (verify ? 4u : 0u);
-  if (!desc && (verify || a.out != nullptr) && (!verify || (a.len_c & 255u) != 0) &&
-      (a.flags & (prismdb::dev::kFlagWriteTrailer | prismdb::dev::kFlagLogHeader)) == 0 &&
-      a.len_c >= 4 && a.len_c <= max_len && (a.len_c & 3u) == 0 &&
-      (a.stride & 3u) == 0 && (reinterpret_cast<uintptr_t>(a.base) & 3u) == 0 &&
-      !g_force_generic.load(std::memory_order_relaxed)) {
-    // A bulk batch (full runs for every wave) claims its runs on demand: the
-    // counters are the stream workspace's block of this call's parity, zero
-    // since the call before zeroed it, and the kernel zeroes the other block
-    // for the call after -- the planner path's scheme, no fill in front.
-    // Smaller batches (one SST file, a pipeline chunk) take no workspace.
-    Workspace* w = nullptr;
-    if (prismdb::dev::fixed_claims(a.n, (uint32_t)groups) && (a.n >> 37) == 0 &&
-        !g_fixed_static.load(std::memory_order_relaxed)) {
-      int rc = 0;
-      if ((w = FindWorkspace(s, rc)) == nullptr) return rc;
-      char* const cb = reinterpret_cast<char*>(w->ws.counters);
-      if (w->dirty) {  // the last call failed after using this block, before its plan kernel
-        hipError_t e = hipMemsetAsync(cb + prismdb::dev::kCounterBlock * (w->pcall & 1u), 0, prismdb::dev::kCounterBlock, s);
-        if (e != hipSuccess) return FailHip(e, "hipMemsetAsync");
-        w->dirty = false;
-      }
-      a.claims = reinterpret_cast<uint32_t*>(cb + prismdb::dev::kCounterBlock * (w->pcall & 1u) + 256);
-      a.zero_next = reinterpret_cast<uint32_t*>(cb + prismdb::dev::kCounterBlock * ((w->pcall + 1u) & 1u));
-      t_last_fixed_claims = a.claims;
-      t_last_fixed_stream = s;
-    } else {
-      t_last_fixed_claims = nullptr;
-    }
-    hipError_t e = prismdb::dev::launch_fixed(a, verify, groups, s);
-    if (e != hipSuccess) return FailHip(e, "fixed kernel launch");  // (not run: its block is still zero)
-    if (w != nullptr) {
-      w->pcall++;  // the next call's block is the one this kernel zeroes
-      (void)hipEventRecord(w->done[w->gen & 1u], s);  // the workspace is in use until here
-    }
-    return 0;
-  }
-  int rc = 0;
-  Workspace* w = FindWorkspace(s, rc);
-  if (w == nullptr) return rc;
-  // Whatever follows, the workspace's events mark the end of this call's
-  // work: the one-launch kernel's own completion (hipExtLaunchKernel's stop
-  // event), or a marker after the planner path's last launch (ordered: it
-  // covers everything before it).
-  struct MarkDone {
-    Workspace* w;
-    hipStream_t s;
-    bool by_launch = false;
-    ~MarkDone() {
-      if (!by_launch) (void)hipEventRecord(w->done[w->gen & 1u], s);
-    }
-  } mark{w, s};
+// The planner path: plan (span records, long spans cut into segments) ->
+// span pass (long spans skipped) -> segment pass -> combine, with the lane
+// kernel and its list in front for log-record batches.  `a` is the batch as
+// RunBatch normalised it, `base_args` as the caller passed it.
+int RunPlanner(DeviceCtx& ctx, const SpanBatch& base_args, SpanBatch& a, bool desc, bool verify, int groups,
+               const Route& r, Workspace* w, hipStream_t s, MarkDone& mark) {
   // Between a fork onto the workspace's side stream and its join, an error
-  // return still joins the side stream back into s (before `mark` records
-  // the done event, which must cover the side stream's kernels: the next
-  // call's growth or reuse of the lists and segment records waits on it).
+  // return still joins the side stream back into s.  This function's local:
+  // it is gone when RunBatch's `mark` records the done event, which must
+  // cover the side stream's kernels (the next call's growth or reuse of the
+  // lists and segment records waits on it).
   struct SideJoin {
     Workspace* w;
     hipStream_t s;
@@ -691,99 +709,25 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
         (void)hipStreamSynchronize(w->side);
     }
   } side_join{w, s};
-  // One launch: <= direct_max spans (2^17), or, by default (wmode 2), a
-  // batch that seals or verifies block trailers (not log records) up to the
-  // kernel's capacity -- the SST-file batches the windows below would
-  // otherwise cut in two.
-  const int wmode = g_windows.load(std::memory_order_relaxed);
-  const bool block_trailers = verify || (a.flags & prismdb::dev::kFlagWriteTrailer) != 0;
-  const bool sst_batch = wmode == 2 && block_trailers && !(a.flags & prismdb::dev::kFlagLogHeader);
-  const bool direct = desc && (route == kRouteDirect ||
-                               (route == kRouteAuto && (a.n <= g_direct_max.load(std::memory_order_relaxed) || sst_batch)));
-  if (direct && a.n <= prismdb::dev::kDirectMaxSpans &&
-      a.n <= 64ull * (uint64_t)groups * (prismdb::dev::kDirectThreads / 64)) {
-    prismdb::dev::DirectWs d{};
-    if ((rc = DirectWorkspace(*w, s, &d)) != 0) return rc;
-    t_last_direct = true;
-    t_last_stats = d.stats;
-    t_last_stream = s;
-    t_last_owned = w->owned;
-    t_last_epoch = g_release_epoch.load(std::memory_order_acquire);
-    mark.by_launch = true;
-    hipError_t e = prismdb::dev::launch_direct(a, verify, groups, d, s, w->done[w->gen & 1u]);
-    return e == hipSuccess ? 0 : FailHip(e, "direct kernel launch");
-  }
-  // Bulk descriptor batches: windows of the one-launch kernel.  By default
-  // (wmode 2) only batches of <= 2 windows that seal or verify block
-  // trailers: TableBuilder / ReadBlock batches, whose spans are block_size-
-  // bounded data blocks plus one index block per file (uniform: the windows'
-  // static runs balance them).  A plain checksum batch has no such shape and
-  // takes the planner's task-balanced slices: 200 000 config-3 spans (1-64
-  // KiB) ran at 57.5 % of the roofline as windows against 70.5 % on the
-  // planner path (profiles/r06/r06s_configs.json, config3_band).
-  const uint64_t wmax = g_direct_max.load(std::memory_order_relaxed);
-  if (desc && route == kRouteAuto && wmax > 0 && a.n > wmax &&
-      (wmode == 1 || (wmode == 2 && a.n <= 2 * wmax && block_trailers)) && !(a.flags & prismdb::dev::kFlagLogHeader))
-    return RunWindows(ctx, base_args, verify, s, wmax);
-  // The span kernel indexes records with 32 bits: cut larger batches.
-  if (a.n > prismdb::dev::kMaxGenericSpans) {
-    for (uint64_t i = 0; i < a.n; i += prismdb::dev::kMaxGenericSpans) {
-      SpanBatch p = base_args;
-      p.n = a.n - i < prismdb::dev::kMaxGenericSpans ? a.n - i : prismdb::dev::kMaxGenericSpans;
-      if (desc) {
-        p.off += i;
-        p.len += i;
-        if (p.init != nullptr) p.init += i;
-      } else {
-        p.base += i * a.stride;
-      }
-      if (p.out != nullptr) p.out += i;
-      if (p.mismatch != nullptr) p.mismatch += i;
-      if ((rc = RunBatch(ctx, p, desc, verify, s, kRoutePlanner)) != 0) return rc;
-    }
-    return 0;
-  }
+  int rc = 0;
   SplitWs ws{};
-  // Short spans first, one per lane (crc32c_lane_kernel); the generic path
-  // below then runs over the list of the others only.
-  const int lane_mode = g_lane_mode.load(std::memory_order_relaxed);
-  const bool lane = desc && (lane_mode > 0 || (lane_mode == 0 && (a.flags & prismdb::dev::kFlagLogHeader)));
+  const bool lane = r.lane;
   // The span kernel's record streams: two per wave of its persistent grid.
   // (Round 4 tried one task sequence per wave here, the one-launch kernel's
   // ring: within +-2 % on the bulk rows, profiles/r04/r04i_configs_*.json;
   // its kernels are in git history: crc32c_kernels.hip at 36498f1.)
   const uint32_t streams = 2u * (uint32_t)groups * prismdb::dev::kWavesPerGroup;
   if ((rc = PlannerWorkspace(*w, s, a.n, streams, lane, &ws)) != 0) return rc;
-  // Counters: the block of this call's parity, zeroed by the previous
-  // planner call's plan kernel (or at the workspace's creation) -- no fill
-  // kernel in front of the call (it and its gap took 6.7 us of a config-5
-  // call, profiles/r05/r05aa_c5_seal/one_call_timeline.csv).
-  static_assert(sizeof(SplitCounters) <= 256, "SplitCounters fills the first 256 B of a counter block");
-  {
-    char* const cb = reinterpret_cast<char*>(w->ws.counters);
-    ws.counters = reinterpret_cast<SplitCounters*>(cb + prismdb::dev::kCounterBlock * (w->pcall & 1u));
-    ws.zero_next = reinterpret_cast<SplitCounters*>(cb + prismdb::dev::kCounterBlock * ((w->pcall + 1u) & 1u));
-  }
-  hipError_t e = hipSuccess;
-  if (w->dirty) {  // the last call failed after using this block, before its plan kernel
-    e = hipMemsetAsync(ws.counters, 0, prismdb::dev::kCounterBlock, s);
-    if (e != hipSuccess) return FailHip(e, "hipMemsetAsync");
-  }
+  CounterBlocks cb{};
+  if ((rc = TakeCounterBlocks(*w, s, &cb)) != 0) return rc;
+  ws.counters = reinterpret_cast<SplitCounters*>(cb.cur);
+  ws.zero_next = reinterpret_cast<SplitCounters*>(cb.next);
   w->dirty = true;  // until this call's plan kernel is enqueued
-  t_last_counters = ws.counters;
-  t_last_stream = s;
-  t_last_direct = false;
-  t_last_owned = w->owned;
-  t_last_epoch = g_release_epoch.load(std::memory_order_acquire);
-  // Sealing: the span kernels leave the trailers to one pass after them
-  // (crc32c_trailer_kernel), which reads the results back -- from scratch
-  // when the caller passed no `out`.  Not behind the lane kernel: it stores
-  // each log record's header crc as the record finishes, and that measured
-  // 5 % faster on ~1 KB WAL records than the pass (3931 against 3739 GB/s,
-  // profiles/r05/r05g_variants_lane_seal.json) -- a lane's store is one of
-  // 64 records' in flight, not a wave-wide stall.
-  const bool trailer_pass = (a.flags & prismdb::dev::kFlagWriteTrailer) != 0 && !lane;
-  if (trailer_pass) {
+  t_last = {kLastPlanner, s, cb.cur, nullptr, r.pair, w->owned, g_release_epoch.load(std::memory_order_acquire)};
+  hipError_t e = hipSuccess;
+  // Sealing by the trailer pass (route_of): it reads the results back --
+  // from scratch when the caller passed no `out`.
+  if (r.trailer_pass) {
     a.flags &= ~prismdb::dev::kFlagWriteTrailer;
     if (a.out == nullptr) {
       if (w->cap_s < a.n) {
@@ -798,9 +742,10 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
   uint32_t* const res_out = a.out;  // the caller's out, or the trailer pass's scratch
   uint8_t* const caller_mm = a.mismatch;
   if (lane) {
-    // The list of the spans the lane kernel does not own is built on the
-    // side stream while the lane kernel runs; the generic path below waits
-    // for it.
+    // Short spans first, one per lane (crc32c_lane_kernel).  The list of the
+    // spans the lane kernel does not own is built on the side stream while
+    // the lane kernel runs; the generic path below runs over that list only
+    // and waits for it.
     if ((rc = SideStream(w)) != 0) return rc;
     e = hipEventRecord(w->fork, s);
     if (e == hipSuccess) e = hipStreamWaitEvent(w->side, w->fork, 0);
@@ -833,10 +778,6 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
   // kernel's tail balanced its waves they all left together, and a config-5
   // call's 2145 segments ran after it, 30-140 us; profiles/r06/r06ag.)
   if ((rc = SideStream(w)) != 0) return rc;
-  // Task-balanced slices need more records than span streams: with n <= the
-  // stream count every stream holds at most one record either way, and the
-  // two slice kernels' launches are ~9 us of a file-sized call.
-  const bool sliced = a.n > streams;
   e = prismdb::dev::launch_plan(a, desc, ws, s, w->fork);
   if (e != hipSuccess) return FailHip(e, "plan kernel launch");
   w->pcall++;  // the next call's block is the one this plan kernel zeroes
@@ -856,29 +797,25 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
   seg.rec = ws.seg_rec;
   e = prismdb::dev::launch_span(seg, false, groups, w->side, w->join);  // the join: its stop event
   if (e != hipSuccess) return FailHip(e, "segment kernel launch");
-  if (sliced) {
+  if (r.sliced) {
     e = prismdb::dev::launch_slices(a, ws, s);
     if (e != hipSuccess) return FailHip(e, "slice kernels launch");
     a.slice_start = ws.slice_start;
     a.nslices_dev = &ws.counters->nslices;
     a.tasks_dev = &ws.counters->tasks;
   }
-  // Large batches of one-task records take the pair-run kernel (its two
-  // streams read adjacent spans); it is launched next to the general one,
-  // and the one whose schedule the scan did not pick leaves at once.
-  a.pair_kernel = a.slice_start != nullptr && a.n >= prismdb::dev::kPairMinSpans && !lane &&
-                          !(a.flags & prismdb::dev::kFlagLogHeader)
-                      ? 1u
-                      : 0u;
-  t_last_pair = a.pair_kernel != 0u;
+  // The pair-run kernel (its two streams read adjacent spans) is launched
+  // next to the general one, and the one whose schedule the scan did not
+  // pick leaves at once.
+  a.pair_kernel = r.pair ? 1u : 0u;
   a.claim = &ws.counters->claim;  // (zeroed with the counters above)
-  a.claims = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws.counters) + 256);
+  a.claims = reinterpret_cast<uint32_t*>(cb.cur + 256);
   e = prismdb::dev::launch_span(a, verify, groups, s);
   if (e != hipSuccess) return FailHip(e, "span kernel launch");
   // The call's last kernel completes the workspace's done event itself (its
   // stop event) instead of a marker after it (MarkDone, on an error return).
   hipEvent_t const done = w->done[w->gen & 1u];
-  if (trailer_pass) {
+  if (r.trailer_pass) {
     // Sealing: the trailers of every span but the long ones go out first,
     // while the segment pass finishes on the side stream; then the join and
     // the combine, which stores the long spans' trailers with their results.
@@ -916,6 +853,62 @@ int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify,
   }
   mark.by_launch = true;
   return 0;
+}
+
+// Every device batch: the route (route_of, crc32c_route.h: the whole rule
+// and its measurements), then that route's launches.
+int RunBatch(DeviceCtx& ctx, const SpanBatch& base_args, bool desc, bool verify, hipStream_t s, Forced forced) {
+  SpanBatch a = base_args;
+  // PRISMDB_CRC32C_UNORDERED is accepted and has no effect: every launch is
+  // in stream order (an any-order launch is not supported on gfx9, and it
+  // measured slower where it ran: 25.9 against 24.9 us per SST file)
+  a.flags &= ~PRISMDB_CRC32C_UNORDERED;
+  a.tabs = ctx.tabs;
+  a.role = prismdb::dev::kRoleSpans;
+  const int groups = Groups(ctx.cus);  // read once: this call's grids and its arithmetic on them
+  const Route r = prismdb::route::route_of({desc, verify, a.out != nullptr, a.n, a.flags, a.len_c, a.stride,
+                                            (uint32_t)reinterpret_cast<uintptr_t>(a.base)},
+                                           groups, ReadKnobs(), forced);
+  if (r.kind == prismdb::route::kFixed) return RunFixed(a, verify, groups, r.claims, s);
+  int rc = 0;
+  Workspace* w = FindWorkspace(s, rc);
+  if (w == nullptr) return rc;
+  // Destroyed when this returns: after everything the route enqueued and
+  // after RunPlanner's side-stream join, which the done event must cover.
+  MarkDone mark{w, s};
+  switch (r.kind) {
+    case prismdb::route::kOneLaunch: return RunDirect(a, verify, groups, w, s, mark);
+    case prismdb::route::kWindows: return RunWindows(ctx, base_args, verify, s, r.window);
+    case prismdb::route::kCut: return RunCut(ctx, base_args, desc, verify, s);
+    default: return RunPlanner(ctx, base_args, a, desc, verify, groups, r, w, s, mark);
+  }
+}
+
+// Both entry points' checks of `flags` against each other and the arguments.
+int CheckFlags(uint32_t flags, const uint8_t* dev_mismatch) {
+  if ((flags & ~(PRISMDB_CRC32C_MASK | PRISMDB_CRC32C_WRITE_TRAILER | PRISMDB_CRC32C_LOG_HEADER |
+                 PRISMDB_CRC32C_UNORDERED)) != 0)
+    return Fail(PRISMDB_CRC32C_EINVAL, "unknown flag bits");
+  if ((flags & PRISMDB_CRC32C_WRITE_TRAILER) && dev_mismatch != nullptr)
+    return Fail(PRISMDB_CRC32C_EINVAL, "WRITE_TRAILER and verify are exclusive");
+  return 0;
+}
+
+// The read-back every last-batch hook shares: `bytes` of the device record of
+// this thread's last batch (a one-launch batch's usage counters, else the
+// call's counter block) into dst, after waiting for its stream.  0; -2 where
+// a planner batch is asked for and the last batch took the one-launch kernel;
+// -1 if the last batch was not of route `want`, or its workspace has been
+// released since -- by this thread (SyncAndRelease cleared the pointer) or,
+// an engine stream's, by any (the epoch): no device access then.
+int ReadLast(LastRoute want, void* dst, size_t bytes, const char* what) {
+  if (want == kLastPlanner && t_last.route == kLastOneLaunch) return -2;
+  const void* src = want == kLastOneLaunch ? static_cast<const void*>(t_last.stats) : t_last.counters;
+  const bool stale = t_last.owned && t_last.epoch != g_release_epoch.load(std::memory_order_acquire);
+  if (t_last.route != want || src == nullptr || stale) return -1;
+  hipError_t e = hipStreamSynchronize(t_last.stream);
+  if (e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+  return e == hipSuccess ? 0 : FailHip(e, what);
 }
 
 }  // namespace
@@ -1005,13 +998,9 @@ int leveldb_crc32c_batch_fixed(const void* dev_base, size_t stride, size_t len, 
   if (nblocks == 0) return 0;
   if (dev_base == nullptr) return Fail(PRISMDB_CRC32C_EINVAL, "dev_base is NULL");
   if (len > 0xFFFFFFFFull) return Fail(PRISMDB_CRC32C_EINVAL, "len must be < 4 GiB");
-  if ((flags & ~(PRISMDB_CRC32C_MASK | PRISMDB_CRC32C_WRITE_TRAILER | PRISMDB_CRC32C_LOG_HEADER |
-                 PRISMDB_CRC32C_UNORDERED)) != 0)
-    return Fail(PRISMDB_CRC32C_EINVAL, "unknown flag bits");
-  if ((flags & PRISMDB_CRC32C_WRITE_TRAILER) && dev_mismatch != nullptr)
-    return Fail(PRISMDB_CRC32C_EINVAL, "WRITE_TRAILER and verify are exclusive");
   DeviceCtx* ctx = nullptr;
-  int rc = GetCtx(&ctx);
+  int rc = CheckFlags(flags, dev_mismatch);
+  if (rc == 0) rc = GetCtx(&ctx);
   if (rc != 0) return rc;
   SpanBatch a{};
   a.base = static_cast<const uint8_t*>(dev_base);
@@ -1022,7 +1011,7 @@ int leveldb_crc32c_batch_fixed(const void* dev_base, size_t stride, size_t len, 
   a.out = dev_out;
   a.mismatch = dev_mismatch;
   a.flags = flags;
-  return RunBatch(*ctx, a, false, dev_mismatch != nullptr, static_cast<hipStream_t>(stream), 0);
+  return RunBatch(*ctx, a, false, dev_mismatch != nullptr, static_cast<hipStream_t>(stream), kRouteAuto);
 }
 
 int leveldb_crc32c_batch(const void* dev_base, const uint64_t* dev_off, const uint32_t* dev_len,
@@ -1031,13 +1020,9 @@ int leveldb_crc32c_batch(const void* dev_base, const uint64_t* dev_off, const ui
   if (n == 0) return 0;
   if (dev_base == nullptr || dev_off == nullptr || dev_len == nullptr)
     return Fail(PRISMDB_CRC32C_EINVAL, "dev_base/dev_off/dev_len must be non-NULL");
-  if ((flags & ~(PRISMDB_CRC32C_MASK | PRISMDB_CRC32C_WRITE_TRAILER | PRISMDB_CRC32C_LOG_HEADER |
-                 PRISMDB_CRC32C_UNORDERED)) != 0)
-    return Fail(PRISMDB_CRC32C_EINVAL, "unknown flag bits");
-  if ((flags & PRISMDB_CRC32C_WRITE_TRAILER) && dev_mismatch != nullptr)
-    return Fail(PRISMDB_CRC32C_EINVAL, "WRITE_TRAILER and verify are exclusive");
   DeviceCtx* ctx = nullptr;
-  int rc = GetCtx(&ctx);
+  int rc = CheckFlags(flags, dev_mismatch);
+  if (rc == 0) rc = GetCtx(&ctx);
   if (rc != 0) return rc;
   SpanBatch a{};
   a.base = static_cast<const uint8_t*>(dev_base);
@@ -1048,7 +1033,7 @@ int leveldb_crc32c_batch(const void* dev_base, const uint64_t* dev_off, const ui
   a.out = dev_out;
   a.mismatch = dev_mismatch;
   a.flags = flags;
-  return RunBatch(*ctx, a, true, dev_mismatch != nullptr, static_cast<hipStream_t>(stream), 0);
+  return RunBatch(*ctx, a, true, dev_mismatch != nullptr, static_cast<hipStream_t>(stream), kRouteAuto);
 }
 
 const char* leveldb_crc32c_last_error(void) { return t_last_error.c_str(); }
@@ -1070,20 +1055,20 @@ void prismdb_crc32c_fixed_static(int on) {
   if (prismdb::TestHooksEnabled()) g_fixed_static.store(on != 0, std::memory_order_relaxed);
 }
 
-// the claims of this thread's last fixed-route batch, summed over its
+// the claims of this thread's last batch, a fixed-route one, summed over its
 // counters: the runs claimed plus one failed claim per wave.  Returns 0 (and
-// *out = 0) after a static batch, -1 before any or on an error.  Call it
-// before the stream's next batch: that one zeroes the block.
+// *out = 0) after a static batch; -1 if the last batch was not a fixed-route
+// one (or there was none), once its workspace has been released (nothing on
+// the device is read then), or with the hooks off.  Call it before the
+// stream's next batch: that one zeroes the block.
 int prismdb_crc32c_last_fixed_claims(uint64_t* out) {
   if (!prismdb::TestHooksEnabled() || out == nullptr) return -1;
   *out = 0;
-  if (t_last_fixed_claims == nullptr) return 0;
+  if (t_last.route == kLastFixedStatic) return 0;
   namespace d = prismdb::dev;
-  uint32_t blk[d::kClaimLines * d::kClaimLineWords];
-  hipError_t e = hipStreamSynchronize(t_last_fixed_stream);
-  if (e == hipSuccess) e = hipMemcpy(blk, t_last_fixed_claims, sizeof(blk), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return FailHip(e, "prismdb_crc32c_last_fixed_claims");
-  for (uint32_t j = 0; j < d::kClaimLines; ++j) *out += blk[d::kClaimLineWords * j];
+  uint32_t blk[d::kCounterBlock / 4];
+  if (int rc = ReadLast(kLastFixedClaims, blk, sizeof(blk), "prismdb_crc32c_last_fixed_claims")) return rc;
+  for (uint32_t j = 0; j < d::kClaimLines; ++j) *out += blk[64 + d::kClaimLineWords * j];
   return 0;
 }
 
@@ -1094,12 +1079,11 @@ void prismdb_crc32c_lane_mode(int mode) {
   g_lane_mode.store(mode > 0 ? 1 : (mode < 0 ? -1 : 0), std::memory_order_relaxed);
 }
 
-// descriptor batches of at most this many spans take the one-launch kernel
-// (clamped to kDirectMaxSpans; 0: none by size -- with prismdb_crc32c_windows
-// at its default 2 a batch that seals or verifies block trailers still takes
-// it up to its capacity, so a test that pins the planner sets windows 0 too;
-// larger batches: windows of this many spans, see prismdb_crc32c_windows);
-// returns the previous value.
+// route::Knobs::direct_max (clamped to kDirectMaxSpans): the size up to which
+// a descriptor batch takes the one-launch kernel, and the window size beyond.
+// What else takes that kernel is route_of's to say (crc32c_route.h;
+// prismdb_crc32c_route answers for a given batch): a test that pins the
+// planner sets prismdb_crc32c_windows(0) too.  Returns the previous value.
 uint64_t prismdb_crc32c_direct_max(uint64_t n) {
   if (!prismdb::TestHooksEnabled()) return g_direct_max.load(std::memory_order_relaxed);
   if (n > prismdb::dev::kDirectMaxSpans) n = prismdb::dev::kDirectMaxSpans;
@@ -1119,10 +1103,10 @@ uint32_t prismdb_crc32c_direct_debug(uint32_t flags) {
   return g_direct_dbg.exchange(flags, std::memory_order_relaxed);
 }
 
-// descriptor batches of more than prismdb_crc32c_direct_max spans (log-record
-// batches aside): 1 = windows of the one-launch kernel, 0 = the planner path,
-// 2 = windows up to two of them, the planner beyond (default); returns the
-// previous value.
+// route::Knobs::windows, for descriptor batches of more than direct_max
+// spans: 1 = windows of the one-launch kernel, 0 = the planner path, 2 = by
+// the batch's shape (default; route_of has the rule).  Out-of-range values
+// count as 2.  Returns the previous value.
 int prismdb_crc32c_windows(int mode) {
   if (!prismdb::TestHooksEnabled()) return g_windows.load(std::memory_order_relaxed);
   return g_windows.exchange(mode < 0 || mode > 2 ? 2 : mode, std::memory_order_relaxed);
@@ -1165,6 +1149,22 @@ int prismdb_crc32c_pair_runs(uint64_t n, uint32_t groups, uint32_t k0, uint32_t 
   return 0;
 }
 
+// The route (prismdb::route::route_of, the function RunBatch switches on) of
+// a batch of this shape on a grid of `groups` workgroups, under the current
+// settings of the routing hooks and the imposed route `forced` (0 = none):
+// out = {kind, claims, window, lane, sliced, pair, trailer_pass}.  Pure host
+// arithmetic: no HIP call, no device.  0, or -1 for n = 0, a grid no launch
+// has or an unknown `forced`.
+int prismdb_crc32c_route(int desc, int verify, int has_out, uint64_t n, uint32_t flags, uint32_t len_c, uint64_t stride,
+                         uint32_t base_lo, uint32_t groups, int forced, uint64_t out[7]) {
+  if (n == 0 || groups == 0 || groups > 65536u || forced < 0 || forced > 2 || out == nullptr) return -1;
+  const Route r = prismdb::route::route_of({desc != 0, verify != 0, has_out != 0, n, flags, len_c, stride, base_lo},
+                                           (int)groups, ReadKnobs(), (Forced)forced);
+  const uint64_t v[7] = {(uint64_t)r.kind, r.claims, r.window, r.lane, r.sliced, r.pair, r.trailer_pass};
+  std::memcpy(out, v, sizeof(v));
+  return 0;
+}
+
 // the call count of the calling thread's workspace for (current device,
 // stream): the next one-launch call there takes gen + 1 (its tag: the low 16
 // bits; gen + 1 == 0 mod 2^16 zeroes the workspace first).  Lets a test cross
@@ -1182,30 +1182,25 @@ int prismdb_crc32c_direct_set_gen(void* stream, uint32_t gen) {
   return -1;
 }
 
-// the cumulative one-launch counters of the workspace of the calling thread's
-// last one-launch batch {tickets adopted, spans folded whole, tickets claimed
-// early, tickets claimed late}, after waiting for its stream.  0, or -1.
+// The read-back hooks below answer for the calling thread's last batch
+// (ReadLast has the return codes): the cumulative one-launch counters of the
+// workspace of that batch, a one-launch one, {tickets adopted, spans folded
+// whole, tickets claimed early, tickets claimed late}, after waiting for its
+// stream.  0, or -1.
 int prismdb_crc32c_direct_stats(uint64_t out[4]) {
-  if (t_last_stats == nullptr || LastBatchStale()) return -1;
   uint32_t c[4] = {0, 0, 0, 0};
-  hipError_t e = hipStreamSynchronize(t_last_stream);
-  if (e == hipSuccess) e = hipMemcpy(c, t_last_stats, sizeof(c), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return FailHip(e, "prismdb_crc32c_direct_stats");
+  if (int rc = ReadLast(kLastOneLaunch, c, sizeof(c), "prismdb_crc32c_direct_stats")) return rc;
   for (int i = 0; i < 4; ++i) out[i] = c[i];
   return 0;
 }
 
-// the split counters of the calling thread's last planner-path descriptor
-// batch {long spans, segments, overflow flag, spans listed by the lane
-// kernel}, after waiting for its stream.  Returns 0; -1 if the thread has run
-// no such batch; -2 if its last descriptor batch took the one-launch path.
+// the split counters of the calling thread's last batch, a planner-path one
+// {long spans, segments, overflow flag, spans listed by the lane kernel},
+// after waiting for its stream.  Returns 0; -2 if the last batch took the
+// one-launch path; -1 if it was no planner batch either, or there was none.
 int prismdb_crc32c_last_split(uint64_t out[4]) {
-  if (t_last_direct) return -2;
-  if (t_last_counters == nullptr || LastBatchStale()) return -1;
   prismdb::dev::SplitCounters c{};
-  hipError_t e = hipStreamSynchronize(t_last_stream);
-  if (e == hipSuccess) e = hipMemcpy(&c, t_last_counters, sizeof(c), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return FailHip(e, "prismdb_crc32c_last_split");
+  if (int rc = ReadLast(kLastPlanner, &c, sizeof(c), "prismdb_crc32c_last_split")) return rc;
   out[0] = c.nlong;
   out[1] = c.nseg;
   out[2] = c.overflow;
@@ -1219,15 +1214,11 @@ int prismdb_crc32c_last_split(uint64_t out[4]) {
 // out[2] = 1 if the host launched the pair-run kernel.  -2 after a one-launch
 // batch, -1 before any planner batch.
 int prismdb_crc32c_last_schedule(uint64_t out[3]) {
-  if (t_last_direct) return -2;
-  if (t_last_counters == nullptr || LastBatchStale()) return -1;
   prismdb::dev::SplitCounters c{};
-  hipError_t e = hipStreamSynchronize(t_last_stream);
-  if (e == hipSuccess) e = hipMemcpy(&c, t_last_counters, sizeof(c), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return FailHip(e, "prismdb_crc32c_last_schedule");
+  if (int rc = ReadLast(kLastPlanner, &c, sizeof(c), "prismdb_crc32c_last_schedule")) return rc;
   out[0] = c.tasks;
   out[1] = c.nslices;
-  out[2] = t_last_pair ? 1u : 0u;
+  out[2] = t_last.pair ? 1u : 0u;
   return 0;
 }
 
@@ -1237,13 +1228,9 @@ int prismdb_crc32c_last_schedule(uint64_t out[3]) {
 // the end; 0 when the batch was too small for a tail), out[1] = the same for
 // the lane kernel's runs.  -2 after a one-launch batch, -1 before any.
 int prismdb_crc32c_last_claims(uint64_t out[2]) {
-  if (t_last_direct) return -2;
-  if (t_last_counters == nullptr || LastBatchStale()) return -1;
   namespace d = prismdb::dev;
   uint32_t blk[d::kCounterBlock / 4];
-  hipError_t e = hipStreamSynchronize(t_last_stream);
-  if (e == hipSuccess) e = hipMemcpy(blk, t_last_counters, sizeof(blk), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return FailHip(e, "prismdb_crc32c_last_claims");
+  if (int rc = ReadLast(kLastPlanner, blk, sizeof(blk), "prismdb_crc32c_last_claims")) return rc;
   d::SplitCounters c{};
   std::memcpy(&c, blk, sizeof(c));
   out[0] = c.claim;  // the span kernel's, plus the pair-run kernel's claim lines

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """SST files per leveldb_crc32c_batch call: µs per file for k = 1..12 files
-per call, sealing and verifying, through tools/variants.py builds: `base`
-(one-launch limit 2^17 spans: 8+ files take two windows) and `direct196k`
-(limit 196 608 spans: one launch while every wave's static run stays <= 64
-spans, up to 11 files).
+per call, sealing and verifying, through tools/variants.py builds.  It
+compared `base` (one-launch limit then 2^17 spans: 8+ files took two windows)
+with a variant `direct196k` (limit 196 608 spans: one launch while every
+wave's static run stays <= 64 spans, up to 11 files), which the product then
+adopted (profiles/r06/r06as_files_per_call.json).
 
-    python tools/variants.py build --only base direct196k
-    python tools/files_per_call.py [lib ...]   # GPU box; one JSON object (default: base direct196k)
+    python tools/variants.py build --only base
+    python tools/files_per_call.py [lib ...]   # GPU box; one JSON object (default: base)
 
 Each row: 143 distinct files (as bench's config5_partitions), calls of k
 files back to back on one stream over them in turn, timed with events around
@@ -46,7 +47,7 @@ def main():
     crc32c.batch(buf, d_off, d_len, mask=True, trailer=True, out=out, check_bounds=False)  # sealed once
     torch.cuda.synchronize()
     res = {}
-    for name in (sys.argv[1:] or ["base", "direct196k"]):
+    for name in (sys.argv[1:] or ["base"]):
         L = ctypes.CDLL(os.path.join(ROOT, "tools", "vlib", f"lib_{name}.so"), mode=os.RTLD_LOCAL)
         L.leveldb_crc32c_batch.restype = ctypes.c_int
         L.leveldb_crc32c_batch.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,

@@ -2,8 +2,8 @@
 """What one leveldb_crc32c_batch_multi call costs over the same batch issued
 with leveldb_crc32c_batch on the caller's stream (measurement support).
 
-    python tools/variants.py build --only base multi_notime ...   # here
-    python tools/multi_ab.py --only base multi_notime             # GPU box
+    python tools/variants.py build --only base multi_direct1 ...   # here
+    python tools/multi_ab.py --only base multi_direct1             # GPU box
 
 One device (ndev = 1: no gather), config 5's per-device batch (2.4 M SST-
 shaped spans sealed), each library's batch_multi and plain batch calls

@@ -49,15 +49,6 @@ VARIANTS = {
     "lane_noseal": [("crc32c_kernels.hip",
                      '          asm volatile("global_store_dword %0, %1, off" : : "v"(ta), "v"(v) : "memory");\n',
                      '          (void)ta;\n')] + MEASURE_ONLY,
-    # the sealing lane kernel's side load of a record's last task reads the
-    # dword holding its header crc (unused: HD is only read at task 0), so
-    # that the line is in L2 when the crc is stored
-    "lane_seal_touch": [("crc32c_kernels.hip",
-                         "    if (kSideAlways || t.k == 0) HD[sl] = asm_load_u32(owned && t.k == 0 ? vp & ~3ull : zero);\n",
-                         "    if (kSideAlways || t.k == 0)\n"
-                         "      HD[sl] = asm_load_u32(owned && t.k == 0 ? vp & ~3ull\n"
-                         "                            : (!kVerify && owned && lastk && (a.flags & kFlagWriteTrailer))\n"
-                         "                                  ? (hdr ? vp - kLogCrcBack : vp + vlen) & ~3ull : zero);\n")],
     # span / fixed kernels at 12 and 8 waves per CU (768- / 512-thread groups)
     "waves12": [("crc32c_device.h", "constexpr int kWavesPerGroup = 16;", "constexpr int kWavesPerGroup = 12;")],
     "waves8": [("crc32c_device.h", "constexpr int kWavesPerGroup = 16;", "constexpr int kWavesPerGroup = 8;")],
@@ -171,69 +162,11 @@ VARIANTS = {
                     "      r.x = (uint32_t)ad;\n      r.y = ((uint32_t)(ad >> 32) & 0xffffu) | (27u << 16);\n"
                     "      r.z = 3988u;\n      r.w = 0xFFFFFFFFu;\n    }\n    return r;\n  };\n"
                     "  auto make = [&](uint32_t b, const SpanRec& r, uint32_t first) -> PTask {\n")] + MEASURE_ONLY,
-    # ... and without the edge-byte load (no tail bytes, no verify there)
-    "pair_noedge": [("crc32c_kernels.hip",
-                     "    if (kVerify && lane >= 6u && lane < 10u) eoff = tl + (lane - 6u);\n    e = buf_ubyte(re, eoff);\n  };\n\n  uint32_t res = 0u, bad = 0u;\n",
-                     "    if (kVerify && lane >= 6u && lane < 10u) eoff = tl + (lane - 6u);\n    (void)eoff;\n    e = 0u;\n  };\n\n  uint32_t res = 0u, bad = 0u;\n"),
-                    ("crc32c_kernels.hip", "  constexpr int kYounger = 2 * (kRounds + 1);  // the other slot's two spans\n",
-                     "  constexpr int kYounger = 2 * kRounds;  // the other slot's two spans\n")] + MEASURE_ONLY,
     # 16 waves per CU with the ticket path folding one chunk per step (its
     # two-chunk steps held 64 VGPRs): does the kernel then fit 128 VGPRs, and
     # do shorter runs per wave (~4 spans of a file instead of ~5.5) pay?
     "w16g1": [("crc32c_device.h", "constexpr int kDirectThreads = 768;", "constexpr int kDirectThreads = 1024;"),
               ("crc32c_direct.hip", "      constexpr int kG = 2;\n", "      constexpr int kG = 1;\n")],
-    # WAL seal, measurement only (ignores neighbouring records' crc words in
-    # the same sector): the lane kernel rewrites the whole aligned 32-B
-    # sector holding a record's crc (loaded with the record's last task)
-    # instead of one unaligned dword.  Does seal then reach verify?
-    "walsec": [
-        ("crc32c_kernels.hip",
-         "__device__ __forceinline__ void wait_lane(u32x4 (&w)[8], uint32_t& hd, uint32_t& ed, uint32_t& sc, uint64_t& noff,\n"
-         "                                          uint32_t& nlen, uint32_t& ninit) {\n"
-         "  asm volatile(\"s_waitcnt vmcnt(8)\"\n"
-         "               : \"+v\"(w[0]), \"+v\"(w[1]), \"+v\"(w[2]), \"+v\"(w[3]), \"+v\"(w[4]), \"+v\"(w[5]), \"+v\"(w[6]),\n"
-         "                 \"+v\"(w[7]), \"+v\"(hd), \"+v\"(ed), \"+v\"(sc), \"+v\"(noff), \"+v\"(nlen), \"+v\"(ninit)\n",
-         "__device__ __forceinline__ void wait_lane(u32x4 (&w)[8], uint32_t& hd, uint32_t& ed, uint32_t& sc, uint64_t& noff,\n"
-         "                                          uint32_t& nlen, uint32_t& ninit, u32x4& sa, u32x4& sb) {\n"
-         "  asm volatile(\"s_waitcnt vmcnt(8)\"\n"
-         "               : \"+v\"(w[0]), \"+v\"(w[1]), \"+v\"(w[2]), \"+v\"(w[3]), \"+v\"(w[4]), \"+v\"(w[5]), \"+v\"(w[6]),\n"
-         "                 \"+v\"(w[7]), \"+v\"(hd), \"+v\"(ed), \"+v\"(sc), \"+v\"(noff), \"+v\"(nlen), \"+v\"(ninit), \"+v\"(sa), \"+v\"(sb)\n"),
-        ("crc32c_kernels.hip", "  uint64_t VP[2];\n  auto issue",
-         "  uint64_t VP[2];\n  u32x4 SA[2] = {}, SB[2] = {};\n  auto issue"),
-        ("crc32c_kernels.hip",
-         "      if (kVerify) SC[sl] = asm_load_u32(owned && lastk ? (hdr ? vp - kLogCrcBack : vp + vlen) : zero);\n    }\n",
-         "      if (kVerify) SC[sl] = asm_load_u32(owned && lastk ? (hdr ? vp - kLogCrcBack : vp + vlen) : zero);\n"
-         "      if (!kVerify) {\n"
-         "        const uint64_t sa = owned && lastk ? ((hdr ? vp - kLogCrcBack : vp + vlen) & ~31ull) : zero;\n"
-         "        asm volatile(\"global_load_dwordx4 %0, %1, off\" : \"=v\"(SA[sl]) : \"v\"(sa));\n"
-         "        asm volatile(\"global_load_dwordx4 %0, %1, off offset:16\" : \"=v\"(SB[sl]) : \"v\"(sa));\n"
-         "      }\n    }\n"),
-        ("crc32c_kernels.hip",
-         "          asm volatile(\"global_store_dword %0, %1, off\" : : \"v\"(ta), \"v\"(v) : \"memory\");\n",
-         "          const uint32_t b = (uint32_t)ta & 31u;\n"
-         "          if (b > 28u) {\n"
-         "            asm volatile(\"global_store_dword %0, %1, off\" : : \"v\"(ta), \"v\"(v) : \"memory\");\n"
-         "          } else {\n"
-         "            const uint32_t sh = 8u * (b & 3u), q = b >> 2;\n"
-         "            const uint64_t v64 = (uint64_t)v << sh, m64 = 0xFFFFFFFFull << sh;\n"
-         "            u32x4 s0 = SA[sl], s1 = SB[sl];\n"
-         "            auto put = [&](uint32_t w, uint32_t d) -> uint32_t {\n"
-         "              w = d == q ? (w & ~(uint32_t)m64) | (uint32_t)v64 : w;\n"
-         "              return d == q + 1u ? (w & ~(uint32_t)(m64 >> 32)) | (uint32_t)(v64 >> 32) : w;\n"
-         "            };\n"
-         "            s0[0] = put(s0[0], 0); s0[1] = put(s0[1], 1); s0[2] = put(s0[2], 2); s0[3] = put(s0[3], 3);\n"
-         "            s1[0] = put(s1[0], 4); s1[1] = put(s1[1], 5); s1[2] = put(s1[2], 6); s1[3] = put(s1[3], 7);\n"
-         "            const uint64_t sa = ta & ~31ull;\n"
-         "            asm volatile(\"global_store_dwordx4 %0, %1, off\" : : \"v\"(sa), \"v\"(s0) : \"memory\");\n"
-         "            asm volatile(\"global_store_dwordx4 %0, %1, off offset:16\" : : \"v\"(sa), \"v\"(s1) : \"memory\");\n"
-         "          }\n"),
-        ("crc32c_kernels.hip", '"+v"(HD[0]), "+v"(ED[0]), "+v"(SC[0]) : : "memory");',
-         '"+v"(HD[0]), "+v"(ED[0]), "+v"(SC[0]), "+v"(SA[0]), "+v"(SB[0]) : : "memory");'),
-        ("crc32c_kernels.hip", "      wait_lane(W[sl], HD[sl], ED[sl], SC[sl], noff, nlen, ninit);\n",
-         "      wait_lane(W[sl], HD[sl], ED[sl], SC[sl], noff, nlen, ninit, SA[sl], SB[sl]);\n"),
-        ("crc32c_kernels.hip", '    asm volatile("" : "+v"(HD[sl]), "+v"(ED[sl]), "+v"(SC[sl]));\n',
-         '    asm volatile("" : "+v"(HD[sl]), "+v"(ED[sl]), "+v"(SC[sl]), "+v"(SA[sl]), "+v"(SB[sl]));\n'),
-    ],
     # measurement-only (trailers not written): the pair-run kernel sealing
     # without its once-per-run trailer stores -- what they cost on bulk SST seals
     "pair_noseal": [("crc32c_kernels.hip",
@@ -275,27 +208,6 @@ VARIANTS["prev"] = [("@src", os.path.join(ROOT, "build", "wt_head", "prismdb_amd
 # and round 6's planner lead-in change alone
 VARIANTS["r05"] = [("@src", os.path.join(ROOT, "build", "wt_0f74c91", "prismdb_amd", "csrc"), None)]
 VARIANTS["r06_parity"] = [("@src", os.path.join(ROOT, "build", "wt_72d150e", "prismdb_amd", "csrc"), None)]
-# walsafe: walsec + the neighbour check (flag bit 26 of the lane's meta)
-VARIANTS["walsafe"] = [
-    (f, o, n.replace("const uint64_t sa = owned && lastk ?", "const uint64_t sa = owned && lastk && ((vmeta >> 26) & 1u) ?")
-            .replace("          if (b > 28u) {\n", "          if (!((meta >> 26) & 1u)) {\n"))
-    for f, o, n in VARIANTS["walsec"]] + [
-    ("crc32c_kernels.hip",
-     "      vmeta = n4 | (q0 << 16) | (h << 21) | (tb << 23) | ((owned ? 1u : 0u) << 25);\n",
-     "      vmeta = n4 | (q0 << 16) | (h << 21) | (tb << 23) | ((owned ? 1u : 0u) << 25);\n"
-     "      {\n"
-     "        const int src = (int)(((lane + 63u) & 63u) << 2);\n"
-     "        const uint32_t plo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)noff);\n"
-     "        const uint32_t phi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)(noff >> 32));\n"
-     "        const uint32_t plen = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)nlen);\n"
-     "        const uint64_t pvp = base + ((uint64_t)phi << 32 | plo);\n"
-     "        const uint64_t ta = vp - kLogCrcBack, sa = ta & ~31ull;\n"
-     "        const uint32_t b = (uint32_t)ta & 31u;\n"
-     "        const bool sec = hdr && owned && b <= 28u && sa + 32u <= vp + vlen &&\n"
-     "                         (b == 0u || (lane != 0u && pvp <= sa && pvp + plen >= ta));\n"
-     "        vmeta |= (sec ? 1u : 0u) << 26;\n"
-     "      }\n"),
-]
 # measurement: the pair-run kernel's per-wave entry and exit times
 # (s_memrealtime, 100 MHz) written after the results (tools/wave_timeline.py)
 VARIANTS["pair_ts"] = [
@@ -458,11 +370,6 @@ VARIANTS["lane_head"] = [("crc32c_kernels.hip", "@git", "HEAD:prismdb_amd/csrc/c
 # written as the whole aligned 32-B sector(s) around it, read first, instead
 # of one 4-B partial write: do full-sector writes beat the partial ones?
 TRAIL_STORE = "    store_le32(t, res[i]);\n  }\n}\n"
-TRAIL_LOOP = ("  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += step) {\n"
-              "    const uint64_t off = kDesc ? a.off[i] : i * a.stride;\n"
-              "    const uint32_t len = kDesc ? a.len[i] : a.len_c;\n"
-              "    const uint8_t* t = hdr ? a.base + off - kLogCrcBack : a.base + off + len;\n"
-              "    store_le32(t, res[i]);\n  }\n}\n")
 VARIANTS["trail_sector"] = [("crc32c_kernels.hip", TRAIL_STORE,
     "    {\n"
     "      const uint64_t ta = reinterpret_cast<uint64_t>(t), s0 = ta & ~31ull, s1 = (ta + 3u) & ~31ull;\n"
@@ -484,21 +391,6 @@ VARIANTS["trail_sector"] = [("crc32c_kernels.hip", TRAIL_STORE,
     "        reinterpret_cast<v4t*>(sa)[1] = v4t{w[4], w[5], w[6], w[7]};\n"
     "      }\n"
     "    }\n  }\n}\n")] + MEASURE_ONLY
-# the trailer pass in 128-thread blocks (twice the blocks)
-VARIANTS["trail_b128"] = [("crc32c_kernels.hip",
-    "  const uint64_t blocks = (a.n + 255u) / 256u;\n  const int grid = (int)(blocks < 16384u ? blocks : 16384u);\n"
-    "  if (desc) crc32c_trailer_kernel<true><<<grid, 256, 0, s>>>(a, res);\n"
-    "  else crc32c_trailer_kernel<false><<<grid, 256, 0, s>>>(a, res);\n",
-    "  const uint64_t blocks = (a.n + 127u) / 128u;\n  const int grid = (int)(blocks < 32768u ? blocks : 32768u);\n"
-    "  if (desc) crc32c_trailer_kernel<true><<<grid, 128, 0, s>>>(a, res);\n"
-    "  else crc32c_trailer_kernel<false><<<grid, 128, 0, s>>>(a, res);\n")]
-# batch_multi without its per-call timing events (t0 / t1 / t2 on the clique
-# streams; prismdb_crc32c_multi_timing then reports nothing) -- what they cost
-VARIANTS["multi_notime"] = [
-    ("crc32c_multi.hip", "    if ((e = hipEventRecord(c->t0[p], c->streams[p])) != hipSuccess) return finish(HipFail(e, \"hipEventRecord\"));\n", ""),
-    ("crc32c_multi.hip", "    if ((e = hipEventRecord(c->t1[p], c->streams[p])) != hipSuccess) return finish(HipFail(e, \"hipEventRecord\"));\n", ""),
-    ("crc32c_multi.hip", "    if ((e = hipEventRecord(c->t2[p], c->streams[p])) != hipSuccess) return finish(HipFail(e, \"hipEventRecord\"));\n", ""),
-    ("crc32c_multi.hip", "  c->timed = true;\n", "")]
 # batch_multi with one device run straight on the caller's stream (no clique
 # stream hand-offs) -- what the hand-offs cost
 VARIANTS["multi_direct1"] = [
@@ -558,19 +450,6 @@ VARIANTS["direct_ts_plain"] = VARIANTS["direct_ts"] + VARIANTS["direct_plain"]
 # (lane_pass -- log-record seals through the trailer pass, -4 %,
 # profiles/r06/r06o -- needs the lane path's scatter before the pass, which
 # the sealing tail no longer runs since the pass moved ahead of the join)
-# the non-temporal trailer pass with four spans per thread, loads first
-VARIANTS["trail_nt4"] = [("crc32c_kernels.hip", TRAIL_LOOP,
-    "  for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < a.n; i0 += step * 4u) {\n"
-    "    const uint8_t* t[4];\n    uint32_t v[4];\n"
-    "#pragma unroll\n    for (uint32_t k = 0; k < 4u; ++k) {\n"
-    "      const uint64_t i = i0 + k * step;\n      t[k] = nullptr;\n      v[k] = 0u;\n"
-    "      if (i < a.n) {\n"
-    "        const uint64_t off = kDesc ? a.off[i] : i * a.stride;\n"
-    "        const uint32_t len = kDesc ? a.len[i] : a.len_c;\n"
-    "        t[k] = hdr ? a.base + off - kLogCrcBack : a.base + off + len;\n        v[k] = res[i];\n      }\n    }\n"
-    "#pragma unroll\n    for (uint32_t k = 0; k < 4u; ++k)\n      if (t[k] != nullptr) store_le32(t[k], v[k]);\n  }\n}\n"),
-    ("crc32c_kernels.hip", "  const uint64_t blocks = (a.n + 255u) / 256u;\n  const int grid = (int)(blocks < 16384u ? blocks : 16384u);\n  if (desc) return launch_k(crc32c_trailer_kernel",
-     "  const uint64_t blocks = (a.n + 1023u) / 1024u;\n  const int grid = (int)(blocks < 16384u ? blocks : 16384u);\n  if (desc) return launch_k(crc32c_trailer_kernel")]
 # the sealing lane kernel's header store held back to the next slot's wait
 # and issued right after it, before that slot's fold: the store's write
 # acknowledgement sits in the in-order vmcnt, and issued at the end of the
@@ -664,11 +543,16 @@ VARIANTS["span8"] = [
      "        if (lane == 0u) got = __hip_atomic_fetch_add(a.claims + kClaimLineWords * cset, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
      "        k = Kst + cset + kClaimLines * rfl(got);\n"),
 ]
-# the one-launch limit raised from 2^17 spans to 196 608 (64 spans per wave
-# at 12 waves x 256 CUs): 8-11 SST files per call in one launch instead of
-# two windows (tools/files_per_call.py)
-VARIANTS["direct196k"] = [("crc32c_device.h", "constexpr uint64_t kDirectMaxSpans = 1ull << 17;",
-                           "constexpr uint64_t kDirectMaxSpans = 196608ull;")]
+# Removed variants: their anchors left the sources (direct196k: the change
+# was adopted).  Their results stay under profiles/:
+#   lane_seal_touch  profiles/r03ac_variants_lane_seal_touch.json
+#   pair_noedge      profiles/r04/r04t_variants.json
+#   walsec           profiles/r04/r04l_variants_w16g1_walsec.json
+#   walsafe          profiles/r04/r04l_variants_w16g1_walsec.json
+#   trail_b128       profiles/r05/r05ai_trailer_pass/variants_sector_b128.json
+#   trail_nt4        profiles/r06/r06s_variants_trail_nt4.json
+#   multi_notime     profiles/r05/r05an_multi_ab.json
+#   direct196k       profiles/r06/r06as_files_per_call.json
 # (trail_plain was adopted in 15de4d0 -- plain stores, four spans per thread,
 # variants trail_x1 / trail_nt there -- and reverted: its dirty lines cost the
 # next call more than the pass saved, profiles/r06/r06n_variants.json)
